@@ -240,6 +240,25 @@ class World:
         return t.tolist()
 
 
+DUMP_SAMPLES = 1 << 21  # solution entries --dump-outputs keeps over all ranks: 16 MB of values + 16 MB of their positions
+
+
+def dump_outputs(d, h, last, rank, size):
+    """--dump-outputs DIR: what a caller of the timed path holds after its last step -- the solution vector (this rank's rows; a
+    fixed, seeded sample of them where they exceed DUMP_SAMPLES / size entries, with the sampled row positions) and the solver's
+    report (iterations, converged, final relative residual) -- as float64 .npy files, so that two builds can be compared output for
+    output on the same inputs.  More than one rank: one set of files per rank, suffixed _rank<r>."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    x = h.solution()
+    k = DUMP_SAMPLES // size
+    idx = np.arange(x.size) if x.size <= k else np.sort(np.random.default_rng(0).choice(x.size, k, replace=False))
+    sfx = "" if size == 1 else f"_rank{rank}"
+    np.save(os.path.join(d, f"solution{sfx}.npy"), x[idx])
+    np.save(os.path.join(d, f"solution_rows{sfx}.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, f"solver_report{sfx}.npy"), np.array([last["iters"], last["converged"], last["final_rel"]], dtype=np.float64))
+
+
 def run(args):
     import hypredrive_amd as hh
     from hypredrive_amd import hypredrv as hd
@@ -393,6 +412,8 @@ def run(args):
     dt = w.reduce([time.perf_counter() - t0], "max")[0]
     if guard is not None:
         guard.cancel()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, h, last, w.rank, w.size)
     PHASE["name"] = "report"
     ms_per_step = dt * 1e3 / args.steps
     cs = hh._lib.comm_stats()
@@ -855,8 +876,12 @@ def main():
     ap.add_argument("--no-traffic", action="store_true", help="N = 1, 256^3: skip the two rocprofv3 --pmc passes behind roofline.traffic "
                     "(the committed profiles/traffic.json is quoted instead)")
     ap.add_argument("--no-extras", action="store_true", help="N > 1: skip the strong_<grid> and n1_reference child launches")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (solution, sampled "
+                    "above 2^21 entries; solver report) as float64 .npy files into DIR")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)  # a launch made by another bench.py: no further children
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     signal.signal(signal.SIGTERM, _on_term)
     if args.n <= 0:
         args.n = 128 if args.workload == "aniso" else 256

@@ -965,16 +965,16 @@ def test_edge_cases(orc, hd, pins):
     assert r["hist"][0] < 1e-12 * np.linalg.norm(b) or r["iters"] <= 1
 
 
-def test_spgemm_batched_equals_unbatched(orc, hd):
+def test_spgemm_batched_equals_unbatched(orc, hd, tmp_path):
     """Force the row-batched SpGEMM path with a tiny hash budget (env read once per process,
     so run in a subprocess)."""
     import os
     import subprocess
     import sys
     code = (
-        "import numpy as np, hypredrive_amd as h\n"
+        "import sys, numpy as np, hypredrive_amd as h\n"
         "A = h.lap7(14,14,14); sm = A.strength(); cf = A.pmis(sm); P = A.interp_extpi(sm, cf)\n"
-        "rp, cj, v = A.rap(P).download(); np.savez('/tmp/_rap_%s.npz' % __import__('os').environ.get('HDA_SPGEMM_SLOTS','d'), rp=rp, cj=cj, v=v)\n")
+        "rp, cj, v = A.rap(P).download(); np.savez(sys.argv[1], rp=rp, cj=cj, v=v)\n")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for slots in ("d", "4096"):
         env = dict(os.environ, PYTHONPATH=root)
@@ -982,8 +982,8 @@ def test_spgemm_batched_equals_unbatched(orc, hd):
             env["HDA_SPGEMM_SLOTS"] = slots
         else:
             env.pop("HDA_SPGEMM_SLOTS", None)
-        subprocess.check_call([sys.executable, "-c", code], env=env, cwd=root)
-    a, b = np.load("/tmp/_rap_d.npz"), np.load("/tmp/_rap_4096.npz")
+        subprocess.check_call([sys.executable, "-c", code, str(tmp_path / f"rap_{slots}.npz")], env=env, cwd=root)
+    a, b = np.load(tmp_path / "rap_d.npz"), np.load(tmp_path / "rap_4096.npz")
     for k in ("rp", "cj", "v"):
         assert np.array_equal(a[k], b[k])
 

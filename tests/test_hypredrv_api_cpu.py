@@ -309,13 +309,12 @@ def test_mgr_nested_krylov_and_cycle_yaml(hd):
     L.HYPREDRV_ErrorCodeClear()
 
 
-REF_EXAMPLES = "/root/reference/examples"
+REF_EXAMPLES = os.path.join(ROOT, "tests", "golden", "ref_examples")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_EXAMPLES), reason="reference tree not present (it never travels to the GPU box)")
 def test_every_reference_example_parses_or_is_refused_by_name():
-    """the reference's own examples/*.yml, read in place, through HYPREDRV_InputArgsParse.  Expected outcome per
-    file in tests/golden/ref_examples_expect.json (names only, no reference text): "accepted"; "fragment" = an include file
+    """the reference's own examples/*.yml (input files, stored unchanged under tests/golden/ref_examples), through
+    HYPREDRV_InputArgsParse.  Expected outcome per file in tests/golden/ref_examples_expect.json: "accepted"; "fragment" = an include file
     without a preconditioner section, rejected by the reference too; "not implemented" = refused with a message that says so.
     Never a grammar error: list-valued include, sequences of flow lists, quoted scalars and MGR cycle strings all parse."""
     import ctypes as C
@@ -323,7 +322,7 @@ def test_every_reference_example_parses_or_is_refused_by_name():
     from hypredrive_amd import hypredrv as hd
     expect = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_examples_expect.json")))
     names = sorted(os.path.basename(f) for f in glob.glob(os.path.join(REF_EXAMPLES, "*.yml")))
-    assert names == sorted(expect), "examples added or removed upstream: regenerate the expectation list"
+    assert names == sorted(expect), "stored examples and the expectation list disagree"
     L = hd.lib()
     cwd = os.getcwd()
     os.chdir(REF_EXAMPLES)
