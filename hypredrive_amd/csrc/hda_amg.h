@@ -134,6 +134,21 @@ void gs_free_check(); // throws if a barrier-free block sweep hit its spin limit
 void gs_sweep_blocks(const DCsr &A, const GsPlan &plan, const double *dinv, const double *b, const double *xin, double *xout,
                      bool forward, bool zero_in, bool b_unchanged = false);
 
+// two-stage Gauss-Seidel (relaxation 11 / 12, hda_twostage.hip): of every row the entries of L, the strictly lower part of the
+// row's block, as one run [lbeg_i, lend_i) of the column-sorted row
+struct TwoStage {
+   DArray<int>        lbeg, lend;    // lbeg empty: no row blocks, L starts at the row start
+   unsigned long long gen = 0;       // DCsr::gen of the matrix they were built for
+   int                nnz = -1, lpr = 4;
+};
+// part: the row blocks' starts (empty or one block: none)
+void two_stage_build(const DCsr &A, const std::vector<int> &part, TwoStage &ts);
+// one sweep u += sum_{k=0..terms} (-D^-1 L)^k dinv .* (b - A u): terms 1 = type 11, 2 = type 12; dinv = weight / a_ii.  r: work
+// vector (residual), z: work vector for z1 (terms 2).  zero_guess: u is the zero vector, not read (no residual product).  halo: ghost
+// refresh of u under the residual (row partitions)
+void two_stage_sweep(const DCsr &A, const TwoStage &ts, const double *dinv, double weight, const double *b, double *u, double *r, double *z,
+                     int terms, bool zero_guess, const HaloPlan *halo = nullptr);
+
 // block-Jacobi ILU(0) of a rank's diagonal block (hda_ilu.hip)
 class Ilu {
  public:
@@ -194,6 +209,10 @@ struct AmgLevel {
    DArray<int>    cf;
    std::vector<int> blk_part; // row blocks of this level (AmgParams::blocks): V + 1 row starts; empty = one block
    DArray<double> dinv_down, dinv_up; // relax_weight / l1 (or / a_ii), per cycle direction
+   // two-stage Gauss-Seidel on this level: L bounds, divisors when neither direction's are the plain diagonal (a coarse relaxation of
+   // its own), the work vector of z1 (type 12)
+   TwoStage       ts;
+   DArray<double> dinv_ts, ts_z;
    DArray<double> f, u, u2, t;
    bool           gs_b_seen = false; // a block sweep of this cycle has already put this level's right-hand side into sweep order
    // row-partitioned runs: ghost refresh plans for the inputs of A_l, P_l, R_l and the

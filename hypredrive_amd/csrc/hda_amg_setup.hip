@@ -2510,9 +2510,12 @@ void amg_rap(const DCsr &A, const DCsr &P, const DCsr &R, DCsr &Ac)
 static bool is_jacobi_type(int t) { return t == 18 || t == 0 || t == 7; }
 static bool is_gs_type(int t) { return t == 3 || t == 4 || t == 6 || t == 8 || t == 13 || t == 14; }
 static bool is_l1_gs_type(int t) { return t == 8 || t == 13 || t == 14; }
+// two-stage Gauss-Seidel (hda_twostage.hip): 11 = one term of the Neumann series of (D + L)^-1 after the Jacobi term, 12 = two.  Not
+// a hybrid Gauss-Seidel type: no level sets, no automatic row blocks; explicit row blocks restrict L to the row's block
+static bool is_two_stage_type(int t) { return t == 11 || t == 12; }
 
 // divisor of the sweep: l1 row sums (18), hypre's "option 4" l1 (13/14/8: a_ii plus half the
-// off-rank row sum) or the plain diagonal (0/7/3/4/6).  Extracting the diagonal is option 4
+// off-rank row sum) or the plain diagonal (0/7/3/4/6/11/12).  Extracting the diagonal is option 4
 // with the ghost part ignored, which is what columns < nrows give.
 // two relaxation types with the same divisors (build_dinv below): the up sweep then uses the down sweep's array -- one pass over A
 // less per level in the setup, and on row blocks one sweep-order copy of the divisors serves both (GsPlan::sd_src)
@@ -2581,6 +2584,16 @@ void Amg::build_smoother_data(int l)
       else build_dinv(Al, prm.relax_up, prm.relax_weight, lv.dinv_up);
       if (gs && !lv.gs.built) build_gs_plan(Al, lv.gs);
    }
+   const bool ts_down = is_two_stage_type(prm.relax_down) || is_two_stage_type(prm.relax_up);
+   const bool ts_last = last && is_two_stage_type(prm.relax_coarse);
+   if (ts_down || ts_last)
+   {
+      two_stage_build(Al, lv.blk_part, lv.ts);
+      // the coarsest level's own two-stage relaxation beside smoothers of another divisor class: its plain-diagonal divisors
+      if (ts_last && !same_divisors(prm.relax_coarse, prm.relax_down) && !same_divisors(prm.relax_coarse, prm.relax_up))
+         build_dinv(Al, prm.relax_coarse, prm.relax_weight, lv.dinv_ts);
+      if (prm.relax_down == 12 || prm.relax_up == 12 || (last && prm.relax_coarse == 12)) lv.ts_z.alloc((size_t)std::max(Al.nrows, 1));
+   }
    if (prm.relax_down == 16 || prm.relax_up == 16 || (last && prm.relax_coarse == 16)) build_cheby(l);
    // complex smoother (amg.c:899-921): ILU(0) of the rank's diagonal block on the first smooth_num_levels
    // levels (counted from the finest level of the whole hierarchy), never on the coarsest
@@ -2625,10 +2638,12 @@ void Amg::build_hierarchy(const DCsr &A)
    // own (denominators over the strong C neighbours of the intermediate point, no sign filter), built from sparse products
    HDA_REQUIRE(prm.interp_type == 6 || prm.interp_type == 17 || prm.interp_type == 3 || prm.interp_type == 8,
                "interpolation type is not implemented on MI355X: extended+i (6), its matrix-matrix form mm-ext+i (17), direct_sep_weights (3) and standard (8) are");
-   auto known = [](int t) { return is_jacobi_type(t) || is_gs_type(t) || t == 16; };
+   auto known = [](int t) { return is_jacobi_type(t) || is_gs_type(t) || is_two_stage_type(t) || t == 16; };
    HDA_REQUIRE(known(prm.relax_down) && known(prm.relax_up),
-               "device V-cycle implements Jacobi (0, 7, 18), hybrid Gauss-Seidel (3, 4, 6, 8, 13, 14) and Chebyshev (16) smoothers");
-   HDA_REQUIRE(prm.relax_coarse == 9 || known(prm.relax_coarse), "coarse relaxation must be Gaussian elimination (9), Jacobi, hybrid Gauss-Seidel or Chebyshev");
+               "device V-cycle implements Jacobi (0, 7, 18), hybrid Gauss-Seidel (3, 4, 6, 8, 13, 14), two-stage Gauss-Seidel (11, 12) and "
+               "Chebyshev (16) smoothers");
+   HDA_REQUIRE(prm.relax_coarse == 9 || known(prm.relax_coarse),
+               "coarse relaxation must be Gaussian elimination (9), Jacobi, hybrid or two-stage Gauss-Seidel or Chebyshev");
    HDA_REQUIRE(prm.cheby_variant == 0 || (prm.relax_down != 16 && prm.relax_up != 16 && prm.relax_coarse != 16),
                "Chebyshev smoother: only variant 0 (the standard polynomial) is implemented");
    HDA_REQUIRE(prm.agg_num_levels <= 0 || (prm.agg_interp_type == 4 && prm.num_functions <= 1),
@@ -3259,6 +3274,15 @@ void Amg::relax(int l, int type, const double *dinv, const double *b, double *&c
    if (type == 16)
    {
       cheby_sweep(l, b, cur, zero_guess, fresh);
+      if (dot_slot >= 0) dot(A.nrows, b, cur, dot_slot);
+      return;
+   }
+   if (is_two_stage_type(type))
+   { // in place: alt holds the residual, the level's ts_z the term z1 (type 12); L never reaches a ghost column
+      AmgLevel &lv = levels[(size_t)l];
+      if (lv.ts.gen != A.gen || lv.ts.nnz != A.nnz) two_stage_build(A, lv.blk_part, lv.ts); // (level 0 rebound to another matrix)
+      const double *dv = same_divisors(type, prm.relax_down) ? lv.dinv_down.data() : same_divisors(type, prm.relax_up) ? lv.dinv_up.data() : lv.dinv_ts.data();
+      two_stage_sweep(A, lv.ts, dv, prm.relax_weight, b, cur, alt, lv.ts_z.data(), type == 11 ? 1 : 2, zero_guess, fresh ? nullptr : &level_hA(l));
       if (dot_slot >= 0) dot(A.nrows, b, cur, dot_slot);
       return;
    }

@@ -275,7 +275,8 @@ extern "C" int hda_relax(hda_csr_t A, int relax_type, double weight, int sweeps,
    const DCsr &m      = A->get();
    const bool  jacobi_t = relax_type == 18 || relax_type == 0 || relax_type == 7;
    const bool  gs_t     = relax_type == 3 || relax_type == 4 || relax_type == 6 || relax_type == 8 || relax_type == 13 || relax_type == 14;
-   HDA_REQUIRE(jacobi_t || gs_t, "device relax: Jacobi (0/7/18) or hybrid Gauss-Seidel (3/4/6/8/13/14)");
+   const bool  ts_t     = relax_type == 11 || relax_type == 12;
+   HDA_REQUIRE(jacobi_t || gs_t || ts_t, "device relax: Jacobi (0/7/18), hybrid Gauss-Seidel (3/4/6/8/13/14) or two-stage Gauss-Seidel (11/12)");
    DArray<double> d((size_t)std::max(m.nrows, 1)), dinv((size_t)std::max(m.nrows, 1)), db, x0, x1;
    if (relax_type == 18) l1_row_norms(m, 1, d.data());
    else if (relax_type == 13 || relax_type == 14 || relax_type == 8) l1_row_norms(m, 4, d.data());
@@ -287,9 +288,17 @@ extern "C" int hda_relax(hda_csr_t A, int relax_type, double weight, int sweeps,
    double *cur = x0.data(), *alt = x1.data();
    GsPlan  plan;
    if (gs_t) build_gs_plan(m, plan);
+   TwoStage       ts;
+   DArray<double> tz;
+   if (ts_t)
+   {
+      two_stage_build(m, {}, ts);
+      if (relax_type == 12) tz.alloc((size_t)std::max(m.nrows, 1));
+   }
    for (int s = 0; s < sweeps; s++)
    {
-      if (jacobi_t)
+      if (ts_t) two_stage_sweep(m, ts, dinv.data(), weight, db.data(), cur, alt, tz.data(), relax_type == 11 ? 1 : 2, false);
+      else if (jacobi_t)
       {
          jacobi(m, dinv.data(), db.data(), cur, alt, -1);
          std::swap(cur, alt);
@@ -311,8 +320,25 @@ extern "C" int hda_relax_blocks(hda_csr_t A, int relax_type, double weight, int 
    HDA_TRY
    const DCsr &m    = A->get();
    const bool  gs_t = relax_type == 3 || relax_type == 4 || relax_type == 6 || relax_type == 8 || relax_type == 13 || relax_type == 14;
-   HDA_REQUIRE(gs_t, "row-block relax: hybrid Gauss-Seidel (3/4/6/8/13/14)");
+   const bool  ts_t = relax_type == 11 || relax_type == 12;
+   HDA_REQUIRE(gs_t || ts_t, "row-block relax: hybrid Gauss-Seidel (3/4/6/8/13/14) or two-stage Gauss-Seidel (11/12)");
    const std::vector<int> hp = to_part(nblk, part, m.nrows);
+   if (ts_t)
+   { // L restricted to every row's block; the divisors are the plain diagonal whatever the blocks
+      TwoStage ts;
+      two_stage_build(m, hp, ts);
+      DArray<double> d((size_t)std::max(m.nrows, 1)), dinv((size_t)std::max(m.nrows, 1)), db, x0, r, tz;
+      extract_diag(m, d.data());
+      make_dinv(m.nrows, d.data(), weight, dinv.data());
+      db.upload(b, (size_t)m.nrows);
+      x0.upload(x, (size_t)std::max(m.ncols, m.nrows));
+      r.alloc((size_t)std::max(m.nrows, 1));
+      if (relax_type == 12) tz.alloc((size_t)std::max(m.nrows, 1));
+      for (int s = 0; s < sweeps; s++) two_stage_sweep(m, ts, dinv.data(), weight, db.data(), x0.data(), r.data(), tz.data(), relax_type == 11 ? 1 : 2, false);
+      HDA_HIP(hipMemcpyAsync(x, x0.data(), sizeof(double) * (size_t)m.nrows, hipMemcpyDeviceToHost, Context::get().stream));
+      Context::get().sync();
+      return HDA_OK;
+   }
    GsPlan plan;
    build_gs_plan_blocks(m, hp, plan);
    DArray<double> d((size_t)std::max(m.nrows, 1)), dinv((size_t)std::max(m.nrows, 1)), db, x0, x1;

@@ -149,7 +149,8 @@ void Amg::reorder_levels()
       if (chk && *chk && *chk != '0') return;
    }
    // Gauss-Seidel sweeps depend on the numbering: hypre's semantics are the natural order
-   auto gs = [](int t) { return t == 3 || t == 4 || t == 6 || t == 8 || t == 13 || t == 14; };
+   // (so do the two-stage sweeps 11 / 12: their L is the lower triangle in that order, found as a prefix of the column-sorted rows)
+   auto gs = [](int t) { return t == 3 || t == 4 || t == 6 || t == 8 || t == 11 || t == 12 || t == 13 || t == 14; };
    if (gs(prm.relax_down) || gs(prm.relax_up) || gs(prm.relax_coarse)) return;
    if (prm.smooth_num_levels > 1) return; // so does an ILU factorisation (level 0 is never renumbered)
    // Row blocks (dist): only the unknowns this rank owns are renumbered -- ghost slots are numbered
