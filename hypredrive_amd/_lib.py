@@ -88,6 +88,7 @@ SYMBOLS = [
     "hda_amd_partitioned_levels", "hda_amd_hierarchy_levels",
     "hda_second_strength", "hda_coarsen_second_pass", "hda_interp_multipass", "hda_truncate_rows",
     "hda_interp_mm_extpi", "hda_interp_standard", "hda_set_overlap", "hda_marker", "hda_relax_blocks", "hda_l1_norms_blocks", "hda_hmis_blocks", "hda_amg_blocks", "hda_amg_level_blocks",
+    "hda_csr_form", "hda_spmv_mode",
 ]
 
 
@@ -194,6 +195,8 @@ def load():
     L.hda_check_row_total.argtypes = [C.c_longlong, C.c_int]
     L.hda_format_bytes.argtypes = [vp, vp, dp, dp, dp, ip]
     L.hda_probe_spmv.argtypes = [vp, C.c_int]
+    L.hda_csr_form.argtypes = [vp, C.c_int, ip]
+    L.hda_spmv_mode.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, dp, dp, dp, dp, dp, dp, dp, dp, dp, ip]
     L.hda_probe_read.argtypes = [dp, ip]
     L.hda_probe_add.argtypes = [vp, C.c_int, ip]
     L.hda_probe_read_id.argtypes = [C.c_int, dp, ip]
@@ -663,6 +666,36 @@ def format_bytes(A, amg=None):
     _check(load().hda_format_bytes(A.h, amg.h if amg is not None else None, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
     return {"pcg_iteration": a.value, "vcycle": b.value, "spmv": c.value, "coded": d.value in (1, 2), "row_coded": d.value == 2,
             "windowed": d.value in (3, 5), "value_coded": d.value in (4, 5)}
+
+
+# kernel ids of csr_form (HDA_FORM_* of include/hypredrv_amd.h) and product modes of spmv_mode (HDA_SPMV_*)
+FORMS = {-1: "none", 0: "lane_group", 1: "stream", 2: "window", 3: "window_runs", 4: "coded", 5: "rowclass"}
+SPMV_MODES = {"plain": 0, "plain_dot": 1, "resid": 2, "jacobi": 3, "jacobi_dot": 4, "scaled_copy": 5}
+
+
+def csr_form(A, nown=-1):
+    """The kernel the product of A runs on: the whole product (nown < 0) or the owned-column half of the split product with nown
+    owned columns.  dict(kernel (a FORMS name), lpr, value_coded, escapes, rc_esc_rows, maxrow, blocks (chunks or windows))."""
+    info = np.zeros(8, dtype=np.int32)
+    _check(load().hda_csr_form(A.h, nown, _ip(info)))
+    return dict(kernel=FORMS[int(info[0])], lpr=int(info[1]), value_coded=bool(info[2]), escapes=int(info[3]),
+                rc_esc_rows=int(info[4]), maxrow=int(info[5]), blocks=int(info[6]))
+
+
+def spmv_mode(A, mode, x, nown=-1, alpha=1.0, beta=0.0, yin=None, in_place=False, b=None, dinv=None, w=None, dinv2=None, y2=None):
+    """One product of the family (a SPMV_MODES name) through the entry the solver uses; nown >= 0: the split product.  in_place:
+    yin is passed as y itself (y starts as yin).  y2: what the scaled copy starts from (rows it leaves alone come back unchanged).
+    Returns dict(y, y2, dot, epilogue_taken)."""
+    n = A.nrows
+    f64 = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float64)
+    x, yin, b, dinv, w, dinv2 = f64(x), f64(yin), f64(b), f64(dinv), f64(w), f64(dinv2)
+    y = yin.copy() if in_place else np.zeros(n)
+    y2 = (np.zeros(n) if y2 is None else f64(y2).copy()) if dinv2 is not None else None
+    p = lambda v: None if v is None else _dp(v)
+    dot, taken = C.c_double(), C.c_int()
+    _check(load().hda_spmv_mode(A.h, SPMV_MODES[mode], nown, alpha, beta, p(x), _dp(y) if in_place else p(yin), p(b), p(dinv), p(w),
+                                p(dinv2), _dp(y), p(y2), C.byref(dot), C.byref(taken)))
+    return dict(y=y, y2=y2, dot=dot.value, epilogue_taken=bool(taken.value))
 
 
 def probe_spmv(A, mode):

@@ -1017,6 +1017,59 @@ extern "C" int hda_format_bytes(hda_csr_t A, hda_amg_t amg, double *pcg_iteratio
    HDA_CATCH
 }
 
+extern "C" int hda_csr_form(hda_csr_t A, int nown, int *info)
+{
+   HDA_TRY
+   if (!A || !info) { g_err = "hda_csr_form: null matrix or info"; return HDA_ERR_ARG; }
+   const DCsr &m = A->get();
+   if (nown > m.ncols) { g_err = "hda_csr_form: nown must lie in [0, ncols] (or be negative: the whole product)"; return HDA_ERR_ARG; }
+   spmv_form_info(m, nown, info);
+   HDA_CATCH
+}
+
+extern "C" int hda_spmv_mode(hda_csr_t A, int mode, int nown, double alpha, double beta, const double *x, const double *yin, const double *b,
+                             const double *dinv, const double *w, const double *dinv2, double *y, double *y2, double *dot, int *epilogue_taken)
+{
+   HDA_TRY
+   auto bad = [](const char *msg) { g_err = std::string("hda_spmv_mode: ") + msg; return HDA_ERR_ARG; };
+   if (!A) return bad("null matrix");
+   const DCsr &m   = A->get();
+   const bool  jac = mode == HDA_SPMV_JACOBI || mode == HDA_SPMV_JACOBI_DOT;
+   if (mode < HDA_SPMV_PLAIN || mode > HDA_SPMV_SCALED_COPY) return bad("unknown mode");
+   if (nown > m.ncols) return bad("nown must lie in [0, ncols] (or be negative: the whole product)");
+   if (!x || !y) return bad("x and y are required");
+   if (mode == HDA_SPMV_PLAIN && beta != 0.0 && !yin) return bad("beta != 0 reads yin");
+   if (mode == HDA_SPMV_PLAIN_DOT && !w) return bad("the fused dot reads w");
+   if ((mode == HDA_SPMV_RESID || jac) && !b) return bad("this mode reads b");
+   if (jac && !dinv) return bad("the Jacobi sweep reads dinv");
+   if (jac && m.nrows > m.ncols) return bad("the Jacobi sweep reads x[i] for every row i: nrows <= ncols");
+   if ((mode == HDA_SPMV_PLAIN_DOT || mode == HDA_SPMV_JACOBI_DOT) && !dot) return bad("a fused dot needs dot");
+   if (mode == HDA_SPMV_SCALED_COPY && (!dinv2 || !y2)) return bad("the scaled copy needs dinv2 and y2");
+   const size_t   nr = (size_t)m.nrows, nc = (size_t)m.ncols;
+   DArray<double> dx, dyin, db, ddinv, dw, ddinv2, dy, dy2;
+   dx.upload(x, nc);
+   dy.upload(y, nr);
+   const bool in_place = yin == y; // yin aliases y on the device as well
+   if (mode == HDA_SPMV_PLAIN && yin && !in_place) dyin.upload(yin, nr);
+   if (b) db.upload(b, nr);
+   if (dinv) ddinv.upload(dinv, nr);
+   if (w) dw.upload(w, nr);
+   if (mode == HDA_SPMV_SCALED_COPY)
+   {
+      ddinv2.upload(dinv2, nr);
+      dy2.upload(y2, nr); // rows the product leaves alone come back as they were given
+   }
+   const double *pyin = (mode != HDA_SPMV_PLAIN || !yin) ? nullptr : in_place ? dy.data() : dyin.data();
+   double        d    = 0.0;
+   bool          taken = false;
+   spmv_test_mode(m, mode, nown, alpha, beta, dx.data(), pyin, db.data(), ddinv.data(), dw.data(), ddinv2.data(), dy.data(), dy2.data(), &d, &taken);
+   dy.download(y, nr);
+   if (mode == HDA_SPMV_SCALED_COPY) dy2.download(y2, nr);
+   if (dot) *dot = d;
+   if (epilogue_taken) *epilogue_taken = taken;
+   HDA_CATCH
+}
+
 // Borrowed seam views of a HYPREDRV object whose solver is set up: its level-0 operator (with the right-hand side and
 // the ghost refresh plan of a row block) and its BoomerAMG hierarchy.  bench.py measures the object the API
 // built, not a second copy.  Valid until LinearSolverDestroy / PreconDestroy; release with hda_csr_destroy / hda_amg_destroy.

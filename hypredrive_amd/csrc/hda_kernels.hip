@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <mutex>
 #include <unordered_map>
@@ -1977,21 +1978,41 @@ struct SpmvEpilogue {
 };
 #define g_epilogue (RankState<SpmvEpilogue>::get())
 
+// The kernel a product of A runs on (whole product, or the owned-column half of a split one), decided as launch_spmv_impl
+// launches: builds the plans it needs (chunk plan, stencil / value coding, windows) on first use.  hda_csr_form reports it.
+static SpmvForm spmv_form(const DCsr &A, bool split)
+{
+   ensure_plan(A);
+   ensure_coded(A);
+   if (A.coded == 1 && spmv_mode() == 0) return A.rowcoded == 1 ? SpmvForm::RowClass : SpmvForm::Coded;
+   // Small operators (the coarse levels of a hierarchy; every level of a small problem) are latency-bound, not bandwidth-bound: what
+   // a product costs there is its chain of dependent memory round trips.  The lane-group kernel has three (row pointer -> entries ->
+   // x); the chunked LDS kernels five and two barriers (chunk table -> row pointers -> entries -> x -> products in LDS -> row
+   // pointers again).  Below small_nnz() entries the lane-group kernel runs (whole products only: it has no owned-column form).
+   const bool small = !split && A.coded != 1 && A.nnz <= small_nnz() && A.nnz > 0;
+   if (spmv_mode() == 0 && A.maxrow <= kMaxRowLds && !small)
+   {
+      ensure_window(A);
+      if (A.win == 1) return A.win_runs ? SpmvForm::WindowRuns : SpmvForm::Window;
+      return SpmvForm::Stream;
+   }
+   return split ? SpmvForm::None : SpmvForm::LaneGroup;
+}
+
 template <int MODE, bool DOT>
 static bool launch_spmv_impl(const DCsr &A, const double *x, double alpha, double beta,
                         const double *yin, const double *b, const double *dinv, const double *w,
                         double *out, double *partial, int nown = -1)
 {
    if (A.nrows == 0 && !DOT) return true;
-   ensure_plan(A);
-   ensure_coded(A);
-   const bool split = nown >= 0;
-   const int  gmax  = split ? overlap_grid() : kRedBlocks;
-   if (A.coded == 1 && spmv_mode() == 0)
+   const bool     split = nown >= 0;
+   const SpmvForm form  = spmv_form(A, split);
+   const int      gmax  = split ? overlap_grid() : kRedBlocks;
+   if (form == SpmvForm::RowClass || form == SpmvForm::Coded)
    {
       const int per  = (((A.nrows + 7) >> 3) + 255) / 256 * 256; // rows per XCD (as in the kernel)
       const int grid = DOT ? gmax : std::min(gmax, 8 * (per / 256));
-      if (A.rowcoded == 1)
+      if (form == SpmvForm::RowClass)
       {
 #define HDA_RC(SPF)                                                                                                                              \
    k_spmv_rowclass<MODE, DOT, SPF><<<grid, 256, 0, STREAM>>>(A.nrows, A.rclass.data(), A.rc_keys.data(), A.dict_val.data(), A.dict_delta.data(),   \
@@ -2010,15 +2031,9 @@ static bool launch_spmv_impl(const DCsr &A, const double *x, double alpha, doubl
                                                                       A.col.data(), A.val.data(), x, alpha, beta, yin, b, dinv, w, out, partial, 0);
       return true;
    }
-   // Small operators (the coarse levels of a hierarchy; every level of a small problem) are latency-bound, not bandwidth-bound: what
-   // a product costs there is its chain of dependent memory round trips.  The lane-group kernel has three (row pointer -> entries ->
-   // x); the chunked LDS kernels five and two barriers (chunk table -> row pointers -> entries -> x -> products in LDS -> row
-   // pointers again).  Below small_nnz() entries the lane-group kernel runs (whole products only: it has no owned-column form).
-   const bool small = !split && A.coded != 1 && A.nnz <= small_nnz() && A.nnz > 0;
-   if (spmv_mode() == 0 && A.maxrow <= kMaxRowLds && !small)
+   if (form == SpmvForm::Stream || form == SpmvForm::Window || form == SpmvForm::WindowRuns)
    {
-      ensure_window(A);
-      if (A.win == 1)
+      if (form != SpmvForm::Stream)
       {
          const int    plen = kWChunk + A.maxrow;
          const size_t wlds = sizeof(double) * (size_t)(plen + A.win_maxu);
@@ -2036,7 +2051,7 @@ static bool launch_spmv_impl(const DCsr &A, const double *x, double alpha, doubl
    k_spmv_win<MODE, DOT, VCF, SPF><<<wg, 256, wlds, STREAM>>>(A.nwin, A.wmeta.data(), A.rowptr.data(), A.lidx.data(), A.ucol.data(),     \
                                                               A.val.data(), x, alpha, beta, yin, b, dinv, w, out, partial, nown, plen,  \
                                                               CODE, DICT, win_pf(), wepi_d, wepi_o)
-         if (A.win_runs)
+         if (form == SpmvForm::WindowRuns)
          { // run form (never value-coded)
             if (split) k_spmv_win<MODE, DOT, false, true, true><<<wg, 256, wlds, STREAM>>>(A.nwin, A.wmeta.data(), A.rowptr.data(), A.lidx.data(), A.ucol.data(), A.val.data(), x, alpha, beta, yin, b, dinv, w, out, partial, nown, plen, nullptr, nullptr, win_pf());
             else k_spmv_win<MODE, DOT, false, false, true><<<wg, 256, wlds, STREAM>>>(A.nwin, A.wmeta.data(), A.rowptr.data(), A.lidx.data(), A.ucol.data(), A.val.data(), x, alpha, beta, yin, b, dinv, w, out, partial, nown, plen, nullptr, nullptr, win_pf(), wepi_d, wepi_o);
@@ -2081,7 +2096,7 @@ static bool launch_spmv_impl(const DCsr &A, const double *x, double alpha, doubl
 #undef HDA_STREAM
       return true;
    }
-   if (split) return false; // the lane-group kernel (very long rows, HDA_SPMV=vector) has no split form: caller exchanges first
+   if (form == SpmvForm::None) return false; // the lane-group kernel (very long rows, HDA_SPMV=vector) has no split form: caller exchanges first
    const int lpr  = pick_lpr(A);
    long      need = ((long)A.nrows * lpr + 511) / 512; // two rows per group
    int       grid = DOT ? kRedBlocks : (int)std::min<long>(std::max<long>(need, 1), kRedBlocks);
@@ -2120,6 +2135,33 @@ static bool overlap_enabled()
    return g_overlap_forced >= 0 ? g_overlap_forced == 1 : Comm::world().async_exchange();
 }
 
+// A product splits into an owned-column part and a ghost-column part unless it runs on the lane-group kernel (rows longer than
+// kMaxRowLds on an operator that is not stencil-coded), which has no owned-column form
+static bool spmv_splittable(const DCsr &A)
+{
+   ensure_plan(A);
+   ensure_coded(A);
+   return spmv_mode() == 0 && (A.coded == 1 || A.maxrow <= kMaxRowLds);
+}
+
+// Split product of a splittable A with nown owned columns, ghost-column part ensure_offd(A, nown) built:
+//   rows' owned-column part (SPLIT kernel) | between() | ghost-column part (k_offd_fix)
+// between() is where a row-partitioned product refreshes the ghost tail of x (launch_spmv_halo); x holds every column afterwards.
+template <int MODE, bool DOT, class Between>
+static void launch_spmv_split(const DCsr &A, int nown, double *x, double alpha, double beta, const double *yin, const double *b,
+                              const double *dinv, const double *w, double *out, double *partial, Between &&between)
+{
+   const OffdPart &O = *A.offd;
+   launch_spmv_impl<MODE, DOT>(A, x, alpha, beta, yin, b, dinv, w, out, partial, nown);
+   between();
+   if (O.nbrows)
+   {
+      const int g = std::min(ceil_div(O.nbrows, 256), DOT ? kRedBlocks / 2 : 4096);
+      k_offd_fix<MODE, DOT><<<g, 256, 0, STREAM>>>(O.nbrows, O.brow.data(), O.rp.data(), O.col.data(), O.val.data(), x, alpha, b, dinv, w, out,
+                                                   partial);
+   }
+}
+
 // Row-partitioned product with the ghost refresh of x under it (SURVEY 2.4 C1 "overlapped with the diag-block SpMV"):
 //   pack the send buffer | rows' owned-column part (SPLIT kernel) || transfer on the communication stream | ghost-column part
 // halo == nullptr or a one-rank run: the plain product.
@@ -2130,23 +2172,14 @@ static void launch_spmv_halo(const DCsr &A, const HaloPlan *halo, double *x, dou
    const bool active = halo && halo_active(*halo);
    if (active && overlap_enabled() && !(MODE == MODE_PLAIN && beta != 0.0 && out == x))
    {
-      ensure_plan(A);
-      ensure_coded(A);
-      const bool splittable = spmv_mode() == 0 && (A.coded == 1 || A.maxrow <= kMaxRowLds);
-      if (splittable)
+      if (spmv_splittable(A))
       {
          ensure_offd(A, halo->nloc);
-         const OffdPart &O = *A.offd;
          halo_pack(*halo, x);
-         launch_spmv_impl<MODE, DOT>(A, x, alpha, beta, yin, b, dinv, w, out, partial, halo->nloc);
-         halo_transfer(*halo, x); // waits for the pack only; RCCL: enqueued, runs beside the kernel above; staged: host-side while it runs
-         halo_wait(*halo);
-         if (O.nbrows)
-         {
-            const int g = std::min(ceil_div(O.nbrows, 256), DOT ? kRedBlocks / 2 : 4096);
-            k_offd_fix<MODE, DOT><<<g, 256, 0, STREAM>>>(O.nbrows, O.brow.data(), O.rp.data(), O.col.data(), O.val.data(), x, alpha, b, dinv, w, out,
-                                                         partial);
-         }
+         launch_spmv_split<MODE, DOT>(A, halo->nloc, x, alpha, beta, yin, b, dinv, w, out, partial, [&] {
+            halo_transfer(*halo, x); // waits for the pack only; RCCL: enqueued, runs beside the kernel above; staged: host-side while it runs
+            halo_wait(*halo);
+         });
          Comm::world().stats.overlapped++;
          return;
       }
@@ -2259,12 +2292,15 @@ void spmv(const DCsr &A, double alpha, const double *x, double beta, const doubl
 {
    launch_spmv<MODE_PLAIN, false>(A, halo, x, alpha, beta, y_in, nullptr, nullptr, nullptr, y_out, nullptr);
 }
+namespace {
+struct EpilogueArmed { // disarmed on every way out: a throwing launch must not leave a stale out2 behind for the next plain product
+   EpilogueArmed(const double *d, double *o) { g_epilogue = SpmvEpilogue{d, o, false}; }
+   ~EpilogueArmed() { g_epilogue = SpmvEpilogue{}; }
+};
+} // namespace
 bool spmv_with_scaled_copy(const DCsr &A, const double *x, double *y, const double *dinv2, double *y2, const HaloPlan *halo)
 {
-   struct Armed { // disarmed on every way out: a throwing launch must not leave a stale out2 behind for the next plain product
-      Armed(const double *d, double *o) { g_epilogue = SpmvEpilogue{d, o, false}; }
-      ~Armed() { g_epilogue = SpmvEpilogue{}; }
-   } armed(dinv2, y2);
+   EpilogueArmed armed(dinv2, y2);
    launch_spmv<MODE_PLAIN, false>(A, halo, x, 1.0, 0.0, nullptr, nullptr, nullptr, nullptr, y, nullptr);
    return g_epilogue.done;
 }
@@ -2282,6 +2318,70 @@ void jacobi(const DCsr &A, const double *dinv, const double *b, const double *x_
       launch_spmv<MODE_JACOBI, true>(A, halo, x_in, 1.0, 0.0, nullptr, b, dinv, nullptr, x_out, Context::get().slot(dot_slot));
    else
       launch_spmv<MODE_JACOBI, false>(A, halo, x_in, 1.0, 0.0, nullptr, b, dinv, nullptr, x_out, nullptr);
+}
+
+// ---- test entries of the product family (hda_csr_form, hda_spmv_mode)
+void spmv_form_info(const DCsr &A, int nown, int info[8])
+{
+   const SpmvForm f = spmv_form(A, nown >= 0);
+   info[0]          = (int)f;
+   info[1]          = f == SpmvForm::LaneGroup ? pick_lpr(A) : 0;
+   info[2]          = A.coded == 2; // value codes: read by the streamed and the list-windowed kernel (the run form is never value-coded)
+   info[3]          = (A.coded == 1 || A.coded == 2) ? A.escapes : 0;
+   info[4]          = f == SpmvForm::RowClass ? A.rc_esc_rows : 0;
+   info[5]          = A.maxrow;
+   info[6]          = f == SpmvForm::Stream ? A.nchunks : (f == SpmvForm::Window || f == SpmvForm::WindowRuns) ? A.nwin : 0;
+   info[7]          = 0;
+}
+
+void spmv_test_mode(const DCsr &A, int mode, int nown, double alpha, double beta, double *x, const double *yin, const double *b, const double *dinv,
+               const double *w, const double *dinv2, double *y, double *y2, double *dot, bool *epilogue_taken)
+{
+   constexpr int slot = 0;
+   const bool    split = nown >= 0;
+   const bool    fused = mode == SPMV_TEST_PLAIN_DOT || mode == SPMV_TEST_JACOBI_DOT;
+   HDA_REQUIRE(mode >= SPMV_TEST_PLAIN && mode <= SPMV_TEST_SCALED_COPY, "spmv_test_mode: unknown mode");
+   HDA_REQUIRE(!split || nown <= A.ncols, "spmv_test_mode: nown must lie in [0, ncols]");
+   HDA_REQUIRE(!split || spmv_splittable(A), "spmv_test_mode: this operator has no split product (rows longer than kMaxRowLds, not stencil-coded)");
+   if (fused) fill(kRedBlocks, std::numeric_limits<double>::quiet_NaN(), Context::get().slot(slot)); // every block partial must be written
+   *epilogue_taken = false;
+   if (!split)
+   { // the entries the solver calls
+      switch (mode)
+      {
+         case SPMV_TEST_PLAIN: spmv(A, alpha, x, beta, yin, y); break;
+         case SPMV_TEST_PLAIN_DOT: spmv_dot(A, x, y, w, slot); break;
+         case SPMV_TEST_RESID: residual(A, x, b, y); break;
+         case SPMV_TEST_JACOBI: jacobi(A, dinv, b, x, y, -1); break;
+         case SPMV_TEST_JACOBI_DOT: jacobi(A, dinv, b, x, y, slot); break;
+         default: *epilogue_taken = spmv_with_scaled_copy(A, x, y, dinv2, y2); break;
+      }
+   }
+   else
+   { // the split product of launch_spmv_halo, with every column of x in place
+      ensure_offd(A, nown);
+      double    *part = Context::get().slot(slot);
+      const auto none = [] {};
+      switch (mode)
+      {
+         case SPMV_TEST_PLAIN: launch_spmv_split<MODE_PLAIN, false>(A, nown, x, alpha, beta, yin, nullptr, nullptr, nullptr, y, nullptr, none); break;
+         case SPMV_TEST_PLAIN_DOT: launch_spmv_split<MODE_PLAIN, true>(A, nown, x, 1.0, 0.0, nullptr, nullptr, nullptr, w, y, part, none); break;
+         case SPMV_TEST_RESID: launch_spmv_split<MODE_RESID, false>(A, nown, x, 1.0, 0.0, nullptr, b, nullptr, nullptr, y, nullptr, none); break;
+         case SPMV_TEST_JACOBI: launch_spmv_split<MODE_JACOBI, false>(A, nown, x, 1.0, 0.0, nullptr, b, dinv, nullptr, y, nullptr, none); break;
+         case SPMV_TEST_JACOBI_DOT: launch_spmv_split<MODE_JACOBI, true>(A, nown, x, 1.0, 0.0, nullptr, b, dinv, nullptr, y, part, none); break;
+         default:
+         {
+            EpilogueArmed armed(dinv2, y2);
+            launch_spmv_split<MODE_PLAIN, false>(A, nown, x, 1.0, 0.0, nullptr, nullptr, nullptr, nullptr, y, nullptr, none);
+            *epilogue_taken = g_epilogue.done;
+         }
+      }
+   }
+   if (fused)
+   {
+      finalize(slot, S_TMP);
+      *dot = read_scalar(S_TMP);
+   }
 }
 
 // ------------------------------------------------------------------ BLAS-1

@@ -244,6 +244,28 @@ double hda_pcg_iteration_bytes(hda_csr_t A);
  * V-cycle, one plain product with A.  Equal to the CSR figures when nothing is coded.  *coded = storage form of A's products:
  * 0 plain CSR, 1 entry-coded stencil operator, 2 row-class coded, 3 windowed CSR, 4 value-coded, 5 value-coded + windowed. */
 int hda_format_bytes(hda_csr_t A, hda_amg_t amg, double *pcg_iteration, double *vcycle, double *spmv, int *coded);
+/* Test entries of the sparse product family.  hda_csr_form reports the kernel the product of A runs on -- the whole product
+ * (nown < 0) or the owned-column half of the split product of a row partition with nown owned columns -- building its plans
+ * (chunks, stencil / row-class / value coding, windows) as the first product would.  info[8]: kernel (HDA_FORM_*), lanes per row
+ * of the lane-group kernel (else 0), value-coded (0 / 1), escapes (entries outside the stencil or value dictionary), CSR rows of a
+ * row-class operator, longest row, chunks (streamed) or windows (windowed) (else 0), 0. */
+enum { HDA_FORM_NONE = -1, HDA_FORM_LANE_GROUP = 0, HDA_FORM_STREAM = 1, HDA_FORM_WINDOW = 2, HDA_FORM_WINDOW_RUNS = 3, HDA_FORM_CODED = 4,
+       HDA_FORM_ROWCLASS = 5 };
+int hda_csr_form(hda_csr_t A, int nown, int *info);
+/* One product of the family on host vectors, through the entry the solver uses:
+ *   HDA_SPMV_PLAIN        y = alpha A x + beta yin  (yin may be y itself; beta == 0 never reads yin)
+ *   HDA_SPMV_PLAIN_DOT    y = A x, *dot = <y, w>
+ *   HDA_SPMV_RESID        y = b - A x
+ *   HDA_SPMV_JACOBI       y = x + dinv .* (b - A x)
+ *   HDA_SPMV_JACOBI_DOT   the same, *dot = <b, y>
+ *   HDA_SPMV_SCALED_COPY  y = A x and y2 = dinv2 .* y where the product's kernel fuses it (*epilogue_taken = 1); else y2 is
+ *                         returned as given
+ * nown < 0: the whole product.  0 <= nown <= ncols: the split product of a row partition -- owned columns [0, nown) first, then
+ * the ghost columns -- with x holding every column; refused where a row-partitioned product would not split.  x has ncols
+ * entries, every other vector nrows. */
+enum { HDA_SPMV_PLAIN = 0, HDA_SPMV_PLAIN_DOT = 1, HDA_SPMV_RESID = 2, HDA_SPMV_JACOBI = 3, HDA_SPMV_JACOBI_DOT = 4, HDA_SPMV_SCALED_COPY = 5 };
+int hda_spmv_mode(hda_csr_t A, int mode, int nown, double alpha, double beta, const double *x, const double *yin, const double *b,
+                  const double *dinv, const double *w, const double *dinv2, double *y, double *y2, double *dot, int *epilogue_taken);
 /* Timing probe: bracket every product launch of `mode` (0 y=Ax, 1 residual, 2 Jacobi sweep) on
  * matrix A (e.g. a view from hda_amg_level_matrix) with HIP events on the library stream;
  * hda_probe_read synchronises and returns the average launch duration.  A = NULL disarms. */
