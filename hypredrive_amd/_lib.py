@@ -26,6 +26,7 @@ class AmgParams(C.Structure):
                 ("cheby_fraction", C.c_double),
                 ("smooth_num_levels", C.c_int), ("smooth_num_sweeps", C.c_int),
                 ("ilu_tri_solve", C.c_int), ("ilu_lower_it", C.c_int), ("ilu_upper_it", C.c_int),
+                ("restrict_type", C.c_int), ("restrict_strong_th", C.c_double), ("restrict_filter_th", C.c_double), ("relax_points", C.c_int),
                 ("agg_num_levels", C.c_int), ("agg_num_paths", C.c_int), ("agg_interp_type", C.c_int),
                 ("agg_pmax", C.c_int), ("agg_trunc_factor", C.c_double),
                 ("blocks", C.c_int), ("block_part", C.POINTER(C.c_int64)), ("struct_size", C.c_int)]
@@ -88,7 +89,7 @@ SYMBOLS = [
     "hda_amd_partitioned_levels", "hda_amd_hierarchy_levels",
     "hda_second_strength", "hda_coarsen_second_pass", "hda_interp_multipass", "hda_truncate_rows",
     "hda_interp_mm_extpi", "hda_interp_standard", "hda_set_overlap", "hda_marker", "hda_relax_blocks", "hda_l1_norms_blocks", "hda_hmis_blocks", "hda_amg_blocks", "hda_amg_level_blocks",
-    "hda_csr_form", "hda_spmv_mode",
+    "hda_csr_form", "hda_spmv_mode", "hda_air_restriction",
 ]
 
 
@@ -196,6 +197,7 @@ def load():
     L.hda_format_bytes.argtypes = [vp, vp, dp, dp, dp, ip]
     L.hda_probe_spmv.argtypes = [vp, C.c_int]
     L.hda_csr_form.argtypes = [vp, C.c_int, ip]
+    L.hda_air_restriction.argtypes = [vp, ip, C.c_int, C.c_double, C.c_double, P(vp), P(C.c_int64)]
     L.hda_spmv_mode.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, dp, dp, dp, dp, dp, dp, dp, dp, dp, ip]
     L.hda_probe_read.argtypes = [dp, ip]
     L.hda_probe_add.argtypes = [vp, C.c_int, ip]
@@ -671,6 +673,18 @@ def format_bytes(A, amg=None):
 # kernel ids of csr_form (HDA_FORM_* of include/hypredrv_amd.h) and product modes of spmv_mode (HDA_SPMV_*)
 FORMS = {-1: "none", 0: "lane_group", 1: "stream", 2: "window", 3: "window_runs", 4: "coded", 5: "rowclass"}
 SPMV_MODES = {"plain": 0, "plain_dot": 1, "resid": 2, "jacobi": 3, "jacobi_dot": 4, "scaled_copy": 5}
+
+
+def air_restriction(A, cf, distance=2, strong_th=0.25, filter_th=0.0):
+    """Approximate ideal restriction (restriction_type air_1 / air_2) of the square operator A for the splitting cf
+    (> 0 C, < 0 F), built on the device.  Returns (R, stats): R a Csr (C points x rows), stats dict(fallback, max_m, small, mid,
+    large) -- rows that fell back to injection, the largest neighbourhood, C rows solved by each tier."""
+    cfa = np.ascontiguousarray(np.concatenate([np.asarray(cf, dtype=np.int32), np.zeros(1, np.int32)]), dtype=np.int32)
+    st = np.zeros(5, dtype=np.int64)
+    out = C.c_void_p()
+    _check(load().hda_air_restriction(A.h, _ip(cfa), int(distance), float(strong_th), float(filter_th), C.byref(out),
+                                      st.ctypes.data_as(C.POINTER(C.c_int64))))
+    return Csr(out), dict(fallback=int(st[0]), max_m=int(st[1]), small=int(st[2]), mid=int(st[3]), large=int(st[4]))
 
 
 def csr_form(A, nown=-1):

@@ -65,6 +65,16 @@ struct AmgParams {
    // V + 1 row starts.
    int                    blocks = 1;
    std::vector<long long> block_part;
+   // approximate ideal restriction (AmgParams -> hda_air.hip): restrict_type 0 = P^T, 1 = air_1, 2 = air_2, with
+   // restriction strength restrict_strong_th and filter restrict_filter_th (HYPRE_BoomerAMGSetRestriction / SetStrongThresholdR /
+   // SetFilterThresholdR)
+   int    restrict_type      = 0;
+   double restrict_strong_th = 0.25, restrict_filter_th = 0.0;
+   // points of every sweep (hypre's grid_relax_points): 0 all, -1 F points, 1 C points.  relax_points 1 = the AIR schedule of the
+   // reference (amg.c:988-1015: all points down and on the coarsest level, F points up, C points on the last up sweep when there are
+   // more than two); points_down / points_up, when not empty, name every sweep of that direction (HYPRE_BoomerAMGSetGridRelaxPoints)
+   int              relax_points = 0;
+   std::vector<int> points_down, points_up;
 };
 int amg_auto_blocks(const DCsr &A); // the setup's choice for blocks = 0
 
@@ -209,6 +219,7 @@ struct AmgLevel {
    DArray<int>    cf;
    std::vector<int> blk_part; // row blocks of this level (AmgParams::blocks): V + 1 row starts; empty = one block
    DArray<double> dinv_down, dinv_up; // relax_weight / l1 (or / a_ii), per cycle direction
+   DArray<double> dinv_pts[2][2];     // F / C relaxation: [direction 0 down, 1 up][0 F points, 1 C points] -- that direction's divisors, 0 elsewhere
    // two-stage Gauss-Seidel on this level: L bounds, divisors when neither direction's are the plain diagonal (a coarse relaxation of
    // its own), the work vector of z1 (type 12)
    TwoStage       ts;
@@ -286,6 +297,10 @@ class Amg {
    void cycle(const double *b, double *x, bool zero_guess, int dot_slot, bool first_sweep_given = false);
    void relax(int l, int type, const double *dinv, const double *b, double *&cur, double *&alt,
               bool zero_guess, int dot_slot);
+   int           sweep_points(int dir, int s) const;    // points of sweep s of direction dir (0 down, 1 up): 0 all, -1 F, 1 C
+   const double *sweep_dinv(int l, int dir, int s);     // divisors of that sweep on level l (masked for F / C sweeps)
+   void          check_air_params() const;              // restriction_type / relaxation points: refusal by name of what is not built
+   bool          needs_cf_in_cycle() const;             // some sweep relaxes F or C points only
    void build_hierarchy(const DCsr &A);
    void build_smoother_data(int l); // divisors (and Gauss-Seidel level sets) of level l on the matrix the cycle uses
    void build_cheby(int l);         // eigenvalue estimate and polynomial of the Chebyshev smoother
@@ -432,5 +447,10 @@ void amg_interp_mm_extpi(const DCsr &A, const unsigned char *smask, const int *c
 void spgemm(const DCsr &X, const DCsr &Y, DCsr &C);
 // hypre_BoomerAMGBuildCoarseOperator: Ac = R*(A*P) with R = P^T
 void amg_rap(const DCsr &A, const DCsr &P, const DCsr &R, DCsr &Ac);
+// approximate ideal restriction (hda_air.hip) for the splitting cf (device; > 0 C, < 0 F): R is nc x n, rows
+// column-sorted.  stats: rows that fell back to injection, the largest neighbourhood, rows solved by the small / mid / large tier
+void air_restriction(const DCsr &A, const int *cf, int distance, double strong_th, double filter_th, DCsr &R, long long stats[5]);
+// dst = src at the F points (sel < 0) or the C points (sel > 0) of cf, 0 elsewhere
+void air_mask_divisors(int n, const int *cf, int sel, const double *src, DArray<double> &dst);
 
 } // namespace hda

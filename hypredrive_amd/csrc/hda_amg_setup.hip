@@ -2584,6 +2584,18 @@ void Amg::build_smoother_data(int l)
       else build_dinv(Al, prm.relax_up, prm.relax_weight, lv.dinv_up);
       if (gs && !lv.gs.built) build_gs_plan(Al, lv.gs);
    }
+   if (!last)
+   { // F / C relaxation (relaxation.points): the divisors of such a sweep, zero outside its point set
+      for (int dir = 0; dir < 2; dir++)
+         for (int s = 0; s < (dir == 0 ? prm.sweeps_down : prm.sweeps_up); s++)
+         {
+            const int pt = sweep_points(dir, s);
+            if (pt == 0 || lv.dinv_pts[dir][pt > 0].size()) continue;
+            HDA_REQUIRE(lv.cf.size() >= (size_t)Al.nrows, "F / C relaxation needs the level's C/F splitting");
+            const DArray<double> &base = (dir == 0 || same_divisors(prm.relax_up, prm.relax_down)) ? lv.dinv_down : lv.dinv_up;
+            air_mask_divisors(Al.nrows, lv.cf.data(), pt, base.data(), lv.dinv_pts[dir][pt > 0]);
+         }
+   }
    const bool ts_down = is_two_stage_type(prm.relax_down) || is_two_stage_type(prm.relax_up);
    const bool ts_last = last && is_two_stage_type(prm.relax_coarse);
    if (ts_down || ts_last)
@@ -2631,6 +2643,58 @@ __global__ __launch_bounds__(256) void k_coarse_dof(int n, const int *__restrict
    if (i < n && cf[i] == 1) dofc[cidx[i]] = dof[i];
 }
 
+// restriction_type and the F / C relaxation schedule (hda_air.hip): what is built, and a refusal by name of the rest
+void Amg::check_air_params() const
+{
+   HDA_REQUIRE(prm.restrict_type != 3 && prm.restrict_type != 4 && prm.restrict_type != 5 && prm.restrict_type != 15,
+               "restriction_type: neumann_air_0/1/2 (3, 4, 5) and air_1.5 (15) are not implemented; p_transpose (0), air_1 (1) and air_2 (2) are");
+   HDA_REQUIRE(prm.restrict_type >= 0 && prm.restrict_type <= 2,
+               "restriction_type: p_transpose (0), air_1 (1) and air_2 (2) are implemented");
+   HDA_REQUIRE(prm.restrict_type == 0 || prm.num_functions <= 1,
+               "approximate ideal restriction (air_1 / air_2) is implemented for scalar problems (num_functions 1), not for systems AMG");
+   HDA_REQUIRE(prm.relax_points == 0 || prm.relax_points == 1, "relaxation.points: all (0) and air (1) are implemented");
+   HDA_REQUIRE(prm.points_down.empty() || (int)prm.points_down.size() == prm.sweeps_down,
+               "relaxation points: the down schedule must name every down sweep");
+   HDA_REQUIRE(prm.points_up.empty() || (int)prm.points_up.size() == prm.sweeps_up, "relaxation points: the up schedule must name every up sweep");
+   for (int dir = 0; dir < 2; dir++)
+   {
+      const int ns    = dir == 0 ? prm.sweeps_down : prm.sweeps_up;
+      bool      fc    = false;
+      for (int s = 0; s < ns; s++)
+      {
+         const int pt = sweep_points(dir, s);
+         HDA_REQUIRE(pt >= -1 && pt <= 1, "relaxation points: every sweep relaxes all (0), F (-1) or C (1) points");
+         fc = fc || pt != 0;
+      }
+      if (!fc) continue;
+      HDA_REQUIRE(is_jacobi_type(dir == 0 ? prm.relax_down : prm.relax_up),
+                  "F- or C-point sweeps (relaxation.points) are implemented for Jacobi-family smoothers (0, 7, 18) only");
+      HDA_REQUIRE(prm.smooth_num_levels <= 0,
+                  "F- or C-point sweeps (relaxation.points) with a complex smoother (smoother.num_levels > 0) are not implemented");
+   }
+}
+int Amg::sweep_points(int dir, int s) const
+{
+   const std::vector<int> &v = dir == 0 ? prm.points_down : prm.points_up;
+   if (!v.empty()) return v[(size_t)s];
+   if (prm.relax_points != 1 || dir == 0) return 0;
+   return (prm.sweeps_up > 2 && s == prm.sweeps_up - 1) ? 1 : -1;
+}
+bool Amg::needs_cf_in_cycle() const
+{
+   for (int dir = 0; dir < 2; dir++)
+      for (int s = 0; s < (dir == 0 ? prm.sweeps_down : prm.sweeps_up); s++)
+         if (sweep_points(dir, s) != 0) return true;
+   return false;
+}
+const double *Amg::sweep_dinv(int l, int dir, int s)
+{
+   AmgLevel  &lv = levels[(size_t)l];
+   const int  pt = (l < num_levels() - 1) ? sweep_points(dir, s) : 0; // (the coarsest level relaxes all points)
+   if (pt != 0) return lv.dinv_pts[dir][pt > 0].data();
+   return (dir == 0 || same_divisors(prm.relax_up, prm.relax_down)) ? lv.dinv_down.data() : lv.dinv_up.data();
+}
+
 void Amg::build_hierarchy(const DCsr &A)
 {
    HDA_REQUIRE(prm.coarsen_type == 8 || prm.coarsen_type == 10, "device AMG setup implements PMIS (8) and, on one rank, HMIS (10) coarsening");
@@ -2648,6 +2712,7 @@ void Amg::build_hierarchy(const DCsr &A)
                "Chebyshev smoother: only variant 0 (the standard polynomial) is implemented");
    HDA_REQUIRE(prm.agg_num_levels <= 0 || (prm.agg_interp_type == 4 && prm.num_functions <= 1),
                "aggressive coarsening: multipass interpolation (aggressive.prolongation_type 4) on a scalar problem is what is implemented");
+   check_air_params();
    A0 = &A;
    a0_dims[0] = A.nrows; a0_dims[1] = A.ncols; a0_dims[2] = A.nnz;
    levels.clear();
@@ -2743,8 +2808,20 @@ void Amg::build_hierarchy(const DCsr &A)
          k_coarse_dof<<<ceil_div(n, 256), 256, 0, STREAM>>>(n, L.cf.data(), cidx.data(), dof_cur.data(), dnext.data());
          dof_cur = std::move(dnext);
       }
-      HDA_TRACE("level %d: transpose", lvl);
-      transpose(L.P, L.R);
+      if (prm.restrict_type == 0)
+      {
+         HDA_TRACE("level %d: transpose", lvl);
+         transpose(L.P, L.R);
+      }
+      else
+      { // approximate ideal restriction on this level's operator and splitting (hda_air.hip)
+         HDA_TRACE("level %d: AIR restriction (distance %d)", lvl, prm.restrict_type);
+         long long st[5];
+         air_restriction(Al, L.cf.data(), prm.restrict_type, prm.restrict_strong_th, prm.restrict_filter_th, L.R, st);
+         if (verbose)
+            fprintf(stderr, "[hda] AIR level %d: %lld C rows, %lld fell back to injection, largest neighbourhood %lld, tiers %lld / %lld / %lld\n", lvl,
+                    st[2] + st[3] + st[4], st[0], st[1], st[2], st[3], st[4]);
+      }
       std::vector<int> next_part;
       if (L.blk_part.size() > 1)
       { // coarse ids ascend with the fine ids of the C points: a block's coarse rows are a contiguous range (a rank's coarse rows)
@@ -2930,7 +3007,13 @@ void Amg::setup_dist(const DCsr &Aloc, const HaloPlan &hA0_, const std::vector<l
          lv.R  = std::move(rl);
          lv.hR = make_halo_plan((int)(hi - lo), parts[(size_t)l], gg);
          tail_len[(size_t)l] = std::max(tail_len[(size_t)l], gg.size());
-         lv.cf.release();
+         if (needs_cf_in_cycle())
+         { // F / C relaxation: the splitting of this rank's rows
+            DArray<int> mine((size_t)std::max<long long>(hi - lo, 1));
+            if (hi > lo) HDA_HIP(hipMemcpyAsync(mine.data(), lv.cf.data() + lo, sizeof(int) * (size_t)(hi - lo), hipMemcpyDeviceToDevice, STREAM));
+            lv.cf = std::move(mine);
+         }
+         else lv.cf.release();
       }
    }
    A0        = &Aloc;
@@ -3392,7 +3475,7 @@ void Amg::apply_offering(const double *b, double *x, int dot_slot)
    if (fs.valid)
    {
       double *d = first_sweep_dest(x);
-      fs.dinv   = levels[0].dinv_down.data();
+      fs.dinv   = sweep_dinv(0, 0, 0);
       fs.dest   = (d == x) ? nullptr : d;
       fs.n      = level_A(0).nrows;
       fs.owner  = this;
@@ -3442,7 +3525,7 @@ void Amg::cycle(const double *b, double *x, bool zero_guess, int dot_slot, bool 
       if (zg && prm.sweeps_down == 0) fill(A.nrows, 0.0, cur);
       for (int s = 0; s < prm.sweeps_down; s++)
       {
-         if (!(s == 0 && first_sweep_done)) relax(l, prm.relax_down, lv.dinv_down.data(), f, cur, alt, zg, -1);
+         if (!(s == 0 && first_sweep_done)) relax(l, prm.relax_down, sweep_dinv(l, 0, s), f, cur, alt, zg, -1);
          zg = false;
       }
       residual(A, cur, f, lv.t.data(), &level_hA(l));
@@ -3451,7 +3534,7 @@ void Amg::cycle(const double *b, double *x, bool zero_guess, int dot_slot, bool 
       // the restriction kernel can do on the value it has just computed (one launch and one pass over f and dinv less per level)
       first_sweep_done = false;
       if (fuse_first && l + 1 < L - 1 && prm.sweeps_down > 0 && is_jacobi_type(prm.relax_down) && !nx.ilu)
-         first_sweep_done = spmv_with_scaled_copy(lv.R, lv.t.data(), nx.f.data(), nx.dinv_down.data(), nx.u.data(), &lv.hR);
+         first_sweep_done = spmv_with_scaled_copy(lv.R, lv.t.data(), nx.f.data(), sweep_dinv(l + 1, 0, 0), nx.u.data(), &lv.hR);
       else
          spmv(lv.R, 1.0, lv.t.data(), 0.0, nullptr, nx.f.data(), &lv.hR);
       sol[l] = cur;
@@ -3494,7 +3577,7 @@ void Amg::cycle(const double *b, double *x, bool zero_guess, int dot_slot, bool 
       {
          const bool last = (l == 0) && (s == prm.sweeps_up - 1);
          // (same smoother both ways: the same divisors, and on row blocks the same sweep-order copy of them)
-         relax(l, prm.relax_up, (same_divisors(prm.relax_up, prm.relax_down) ? lv.dinv_down : lv.dinv_up).data(), fl, c, a, false, last ? dot_slot : -1);
+         relax(l, prm.relax_up, sweep_dinv(l, 1, s), fl, c, a, false, last ? dot_slot : -1);
       }
       ghosts_fresh_ = false; // (no post-smoothing sweep consumed it)
       sol[l] = c;
@@ -4297,6 +4380,8 @@ void Amg::setup_dist_partitioned(const DCsr &Aloc, const HaloPlan &hA0_, const s
    HDA_REQUIRE(prm.coarsen_type == 8 && prm.interp_type == 6 && prm.num_functions <= 1,
                "partitioned setup: scalar PMIS + extended+i only");
    HDA_REQUIRE(prm.agg_num_levels <= 0, "partitioned setup: aggressive coarsening needs the replicated setup (the second strength graph reaches two ghost layers deep)");
+   HDA_REQUIRE(prm.restrict_type == 0 && !needs_cf_in_cycle(),
+               "partitioned setup: approximate ideal restriction and F / C relaxation need the replicated setup");
    const long long rep_rows = replicate_rows(cm.size);
    const bool verbose = getenv("HDA_VERBOSE") != nullptr;
    // HDA_GHOST_PROLONG=0: the prolongation leaves ghost copies alone and the post-smoothing sweep refreshes them (4 exchanges per

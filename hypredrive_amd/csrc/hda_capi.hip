@@ -114,6 +114,8 @@ extern "C" void hda_amg_default_params(hda_amg_params *p)
    p->cheby_fraction = d.cheby_fraction;
    p->smooth_num_levels = d.smooth_num_levels; p->smooth_num_sweeps = d.smooth_num_sweeps;
    p->ilu_tri_solve = d.ilu.tri_solve; p->ilu_lower_it = d.ilu.lower_it; p->ilu_upper_it = d.ilu.upper_it;
+   p->restrict_type = d.restrict_type; p->restrict_strong_th = d.restrict_strong_th; p->restrict_filter_th = d.restrict_filter_th;
+   p->relax_points = d.relax_points;
    p->agg_num_levels = d.agg_num_levels; p->agg_num_paths = d.agg_num_paths; p->agg_interp_type = d.agg_interp_type;
    p->agg_pmax = d.agg_pmax; p->agg_trunc_factor = d.agg_trunc_factor;
    p->blocks = d.blocks; p->block_part = nullptr;
@@ -142,6 +144,8 @@ static AmgParams to_params(const hda_amg_params *p)
    a.cheby_fraction = p->cheby_fraction;
    a.smooth_num_levels = p->smooth_num_levels; a.smooth_num_sweeps = p->smooth_num_sweeps;
    a.ilu.tri_solve = p->ilu_tri_solve; a.ilu.lower_it = p->ilu_lower_it; a.ilu.upper_it = p->ilu_upper_it;
+   a.restrict_type = p->restrict_type; a.restrict_strong_th = p->restrict_strong_th; a.restrict_filter_th = p->restrict_filter_th;
+   a.relax_points = p->relax_points;
    a.agg_num_levels = p->agg_num_levels; a.agg_num_paths = p->agg_num_paths; a.agg_interp_type = p->agg_interp_type;
    a.agg_pmax = p->agg_pmax; a.agg_trunc_factor = p->agg_trunc_factor;
    a.blocks = p->blocks;
@@ -582,6 +586,27 @@ extern "C" int hda_rap(hda_csr_t A, hda_csr_t P, hda_csr_t *Ac)
    amg_rap(A->get(), P->get(), R, h->m);
    Context::get().sync();
    *Ac = h.release();
+   HDA_CATCH
+}
+
+extern "C" int hda_air_restriction(hda_csr_t A, const int *cf, int distance, double strong_th, double filter_th, hda_csr_t *R, int64_t stats[5])
+{
+   HDA_TRY
+   HDA_REQUIRE(A && R && stats, "hda_air_restriction: A, R and stats are required");
+   const DCsr &m = A->get();
+   HDA_REQUIRE(m.nrows == m.ncols, "hda_air_restriction: the operator must be square");
+   HDA_REQUIRE(cf || m.nrows == 0, "hda_air_restriction: cf is required");
+   HDA_REQUIRE(distance == 1 || distance == 2, "hda_air_restriction: distance must be 1 (air_1) or 2 (air_2)");
+   HDA_REQUIRE(std::isfinite(strong_th) && strong_th >= 0.0 && std::isfinite(filter_th) && filter_th >= 0.0,
+               "hda_air_restriction: strong_th and filter_th must be finite and >= 0");
+   DArray<int> dcf;
+   dcf.upload(cf, (size_t)m.nrows);
+   auto      h = std::make_unique<hda_csr_s>();
+   long long st[5];
+   air_restriction(m, m.nrows ? dcf.data() : nullptr, distance, strong_th, filter_th, h->m, st);
+   Context::get().sync();
+   for (int q = 0; q < 5; q++) stats[q] = st[q];
+   *R = h.release();
    HDA_CATCH
 }
 

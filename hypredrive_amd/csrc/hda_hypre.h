@@ -73,6 +73,10 @@ struct hypre_Solver_struct {
    HYPRE_PtrToSolverFcn      precond = nullptr, precond_setup = nullptr;
    HYPRE_Solver              precond_solver = nullptr;
    std::unique_ptr<hda::Amg> amg;
+   // HYPRE_BoomerAMGSetGridRelaxPoints: a copy of the schedule (down, up, coarse; one entry per sweep as the sweep counts were when it
+   // was set), checked at Setup
+   bool                      grid_points_set = false;
+   std::vector<int>          grid_points[3];
    // HYPRE_ILU* handle, and the ILU arguments of BoomerAMG's complex smoother (HYPRE_BoomerAMGSetILU*)
    std::unique_ptr<hda::Ilu> ilu;
    hda::IluParams            ilup;

@@ -1161,8 +1161,8 @@ extern "C" HYPRE_Int HYPRE_BoomerAMGDestroy(HYPRE_Solver s)
 
 HY_SETTER(HYPRE_BoomerAMGSetInterpType, HYPRE_Int, s->ap.interp_type = v)
 HY_SETTER(HYPRE_BoomerAMGSetRestriction, HYPRE_Int, s->restriction = v)
-HY_SETTER(HYPRE_BoomerAMGSetStrongThresholdR, HYPRE_Real, (void)v)
-HY_SETTER(HYPRE_BoomerAMGSetFilterThresholdR, HYPRE_Real, (void)v)
+HY_SETTER(HYPRE_BoomerAMGSetStrongThresholdR, HYPRE_Real, s->ap.restrict_strong_th = v)
+HY_SETTER(HYPRE_BoomerAMGSetFilterThresholdR, HYPRE_Real, s->ap.restrict_filter_th = v)
 HY_SETTER(HYPRE_BoomerAMGSetCoarsenType, HYPRE_Int, s->ap.coarsen_type = v)
 HY_SETTER(HYPRE_BoomerAMGSetSabs, HYPRE_Int, s->sabs = v)
 HY_SETTER(HYPRE_BoomerAMGSetTol, HYPRE_Real, s->ap.tol = v)
@@ -1253,6 +1253,21 @@ extern "C" HYPRE_Int HYPRE_BoomerAMGSetCycleNumSweeps(HYPRE_Solver s, HYPRE_Int 
    return 0;
 }
 
+// the points every sweep relaxes (reference amg.c:988-1015 builds the AIR schedule): [1] down, [2] up, [3] coarsest, one entry per sweep
+// of the counts set so far ([0] unused, as in hypre).  Copied: hypre takes the arrays over, this library does not.  NULL is refused
+// as in hypre; the schedule itself is checked at Setup
+extern "C" HYPRE_Int HYPRE_BoomerAMGSetGridRelaxPoints(HYPRE_Solver s, HYPRE_Int **pts)
+{
+   if (!s) return hypre_set_error(HYPRE_ERROR_ARG, "HYPRE_BoomerAMGSetGridRelaxPoints: null solver");
+   if (!pts) return hypre_set_error(HYPRE_ERROR_ARG, "HYPRE_BoomerAMGSetGridRelaxPoints: null grid_relax_points");
+   const int ns[3] = {std::max(s->ap.sweeps_down, 0), std::max(s->ap.sweeps_up, 0), std::max(s->ap.sweeps_coarse, 0)};
+   for (int k = 0; k < 3; k++)
+      if (ns[k] > 0 && !pts[k + 1]) return hypre_set_error(HYPRE_ERROR_ARG, "HYPRE_BoomerAMGSetGridRelaxPoints: a direction with sweeps has no points");
+   for (int k = 0; k < 3; k++) s->grid_points[k].assign(pts[k + 1], pts[k + 1] + ns[k]);
+   s->grid_points_set = true;
+   return 0;
+}
+
 extern "C" HYPRE_Int HYPRE_BoomerAMGSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector, HYPRE_ParVector)
 {
    HY_NEED_DEVICE;
@@ -1280,7 +1295,25 @@ extern "C" HYPRE_Int HYPRE_BoomerAMGSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, 
    s->ap.ilu               = s->ilup;
    HDA_REQUIRE(s->cycle_type == 1, "only V-cycles (cycle type 1) are implemented");
    HDA_REQUIRE(s->filter_functions == 0 || s->num_functions <= 1, "coarsening.filter_functions is not implemented for systems AMG");
-   HDA_REQUIRE(s->restriction == 0, "only P^T restriction (restriction_type 0) is implemented");
+   HDA_REQUIRE(s->restriction != 3 && s->restriction != 4 && s->restriction != 5 && s->restriction != 15,
+               "restriction_type: neumann_air_0/1/2 (3, 4, 5) and air_1.5 (15) are not implemented; p_transpose (0), air_1 (1) and air_2 (2) are");
+   HDA_REQUIRE(s->restriction >= 0 && s->restriction <= 2, "restriction_type: p_transpose (0), air_1 (1) and air_2 (2) are implemented");
+   s->ap.restrict_type = s->restriction;
+   s->ap.points_down.clear();
+   s->ap.points_up.clear();
+   if (s->grid_points_set)
+   { // the schedule: all points on the coarsest level, all / F / C points on every down and up sweep
+      HDA_REQUIRE((int)s->grid_points[0].size() == std::max(s->ap.sweeps_down, 0) && (int)s->grid_points[1].size() == std::max(s->ap.sweeps_up, 0) &&
+                      (int)s->grid_points[2].size() == std::max(s->ap.sweeps_coarse, 0),
+                  "relaxation points (HYPRE_BoomerAMGSetGridRelaxPoints) were set for other sweep counts than the cycle has");
+      for (int p : s->grid_points[2])
+         HDA_REQUIRE(p == 0, "relaxation points: the coarsest level relaxes all points (F- or C-point sweeps there are not implemented)");
+      for (int k = 0; k < 2; k++)
+         for (int p : s->grid_points[k])
+            HDA_REQUIRE(p >= -1 && p <= 1, "relaxation points: every down / up sweep relaxes all (0), F (-1) or C (1) points");
+      s->ap.points_down = s->grid_points[0];
+      s->ap.points_up   = s->grid_points[1];
+   }
    HDA_REQUIRE(s->relax_order == 0, "only lexicographic relaxation order (relaxation.order 0) is implemented");
    s->ap.num_functions = std::max(s->num_functions, 1);
    // row blocks (the reference's hybrid Gauss-Seidel / HMIS at np = V on one GPU): HDA_BLOCKS = V, 1 = the sequential algorithms,
@@ -1299,11 +1332,13 @@ extern "C" HYPRE_Int HYPRE_BoomerAMGSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, 
       // the specification the partitioned setup is checked against (HDA_DIST_CHECK=1)
       const char *mode = getenv("HDA_DIST_SETUP");
       // (HMIS = sequential Ruge pass: only the replicated scheme can run it, on the gathered operator)
+      // (approximate ideal restriction: a neighbourhood reaches past the rank's rows -- hypre fetches the off-rank rows -- and F / C
+      //  sweeps need every level's splitting: both are built on the gathered operator)
       // (aggressive levels: their second strength graph reaches two ghost layers deep -- built on the gathered operator too)
       // (mm-ext+i, type 17: its sparse products are formed on the gathered operator as well; direct (3) and standard (8) interpolation:
       //  options beside the path, one-rank kernels)
       if ((mode && !strcmp(mode, "replicated")) || s->ap.coarsen_type != 8 || s->ap.num_functions > 1 || s->ap.smooth_num_levels > 1 || s->ap.agg_num_levels > 0 ||
-          s->ap.interp_type != 6)
+          s->ap.interp_type != 6 || s->ap.restrict_type != 0 || !s->ap.points_down.empty() || !s->ap.points_up.empty())
          s->amg->setup_dist(A->A, A->halo, A->part, A->ghost_gids);
       else s->amg->setup_dist_partitioned(A->A, A->halo, A->part, A->ghost_gids);
    }
@@ -1741,8 +1776,6 @@ HY_FSAI_PARAM(HYPRE_BoomerAMGSetFSAIKapTolerance, HYPRE_Real)
 
 #define HY_REFUSED(fn, args, what) \
    extern "C" HYPRE_Int fn args { return hypre_set_error(HYPRE_ERROR_GENERIC, #fn ": " what " is not part of the MI355X solve path (SURVEY 8: out of scope)"); }
-// relaxation.points = 1 (C/F-ordered sweeps of the AIR preset, amg.c:988-1015)
-HY_REFUSED(HYPRE_BoomerAMGSetGridRelaxPoints, (HYPRE_Solver, HYPRE_Int **), "C/F-ordered relaxation (relaxation.points)")
 // coarsening.nodal with rigid-body-mode interpolation vectors (amg.c:1017-1032)
 HY_REFUSED(HYPRE_BoomerAMGSetNodal, (HYPRE_Solver, HYPRE_Int), "nodal coarsening")
 HY_REFUSED(HYPRE_BoomerAMGSetNodalDiag, (HYPRE_Solver, HYPRE_Int), "nodal coarsening")

@@ -1688,6 +1688,17 @@ static void amg_create(const AmgArgs &a, HYPRE_Solver *out)
    HYPRE_BoomerAMGSetCycleNumSweeps(p, a.up_sweeps > -1 ? a.up_sweeps : a.num_sweeps, 2);
    HYPRE_BoomerAMGSetCycleRelaxType(p, a.coarse_type, 3);
    HYPRE_BoomerAMGSetCycleNumSweeps(p, a.coarse_sweeps > -1 ? a.coarse_sweeps : a.num_sweeps, 3);
+   // relaxation.points: air (amg.c:988-1015): all points down and on the coarsest level, F points up, C points on the last up sweep
+   // when there are more than two
+   if (a.points == 1)
+   {
+      const int        nd = a.down_sweeps > -1 ? a.down_sweeps : a.num_sweeps, nu = a.up_sweeps > -1 ? a.up_sweeps : a.num_sweeps,
+                       ncs = a.coarse_sweeps > -1 ? a.coarse_sweeps : a.num_sweeps;
+      std::vector<int> down((size_t)std::max(nd, 1), 0), up((size_t)std::max(nu, 1), -1), coarse((size_t)std::max(ncs, 1), 0);
+      if (nu > 2) up[(size_t)nu - 1] = 1;
+      HYPRE_Int *pts[4] = {nullptr, down.data(), up.data(), coarse.data()};
+      HYPRE_BoomerAMGSetGridRelaxPoints(p, pts);
+   }
    *out = p;
 }
 

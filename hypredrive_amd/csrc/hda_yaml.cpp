@@ -264,6 +264,7 @@ static const StrMap kInterp = {{"mod_classical", 0}, {"least_squares", 1}, {"mod
                                {"standard", 8}, {"standard_sep_weights", 9}, {"blk_classical", 10}, {"blk_classical_diag", 11},
                                {"f_f", 12}, {"f_f1", 13}, {"extended", 14}, {"mm_extended", 16}, {"mm_extended+i", 17},
                                {"mm-ext+i", 17}, {"mm_extended+e", 18}, {"mm-ext+e", 18}, {"blk_direct", 24}, {"one_point", 100}};
+static const StrMap kPoints = {{"all", 0}, {"air", 1}}; // relaxation.points (reference src/internal/amg.c:400-408)
 static const StrMap kRestrict = {{"p_transpose", 0}, {"air_1", 1}, {"air_2", 2}, {"neumann_air_0", 3}, {"neumann_air_1", 4},
                                  {"neumann_air_2", 5}, {"air_1.5", 15}};
 static const StrMap kCoarsen = {{"cljp", 0}, {"rs", 1}, {"rs3", 3}, {"falgout", 6}, {"pmis", 8}, {"hmis", 10}};
@@ -736,9 +737,12 @@ static void amg_fields(Ctx &c, YNode &sec, AmgArgs &a)
                               {"up_type", &a.up_type, nullptr, &kRelax}, {"coarse_type", &a.coarse_type, nullptr, &kRelax},
                               {"down_sweeps", &a.down_sweeps, nullptr, nullptr}, {"up_sweeps", &a.up_sweeps, nullptr, nullptr},
                               {"coarse_sweeps", &a.coarse_sweeps, nullptr, nullptr}, {"num_sweeps", &a.num_sweeps, nullptr, nullptr},
-                              {"order", &a.order, nullptr, nullptr}, {"points", &a.points, nullptr, nullptr},
+                              {"order", &a.order, nullptr, nullptr}, {"points", &a.points, nullptr, &kPoints},
                               {"weight", nullptr, &a.weight, nullptr}, {"outer_weight", nullptr, &a.outer_weight, nullptr}},
                       {"chebyshev"});
+         for (auto &q : k->kids)
+            if (q->key == "points" && a.points != 0 && a.points != 1)
+               c.fail(ERR_INVALID_VAL, "invalid value '" + q->val + "' for key 'points' (all / 0 or air / 1)");
          for (auto &q : k->kids)
             if (q->key == "chebyshev")
                apply_fields(c, *q, {{"order", &a.cheby_order, nullptr, nullptr}, {"eig_est", &a.cheby_eig_est, nullptr, nullptr},

@@ -46,6 +46,12 @@ typedef struct {
    /* complex smoother (src/internal/amg.c:899-921), ILU only: bj-iluk, fill 0, natural order on levels < smooth_num_levels */
    int      smooth_num_levels, smooth_num_sweeps;
    int      ilu_tri_solve, ilu_lower_it, ilu_upper_it; /* ILU_args tri_solve / lower_jac_iters / upper_jac_iters (ilu.c:21-23) */
+   /* interpolation.restriction_type / restrict_strong_th / restrict_filter_th (src/internal/amg.c:870-874): 0 P^T, 1 air_1, 2 air_2
+    * (approximate ideal restriction); relaxation.points (amg.c:988-1015): 0 all, 1 the AIR schedule (all points
+    * down and on the coarsest level, F points up, C points on the last up sweep when there are more than two) */
+   int      restrict_type;
+   double   restrict_strong_th, restrict_filter_th;
+   int      relax_points;
    /* AMGagg_args (src/internal/amg.c:160-173, forwarded at :938-944): aggressive coarsening on the first agg_num_levels levels
     * (second PMIS pass over the graph of >= agg_num_paths paths of length <= 2), multipass interpolation (agg_interp_type 4) there */
    int      agg_num_levels, agg_num_paths, agg_interp_type;
@@ -130,6 +136,10 @@ int hda_interp_mm_extpi(hda_csr_t A, const unsigned char *smask, const int *cf, 
 int hda_interp_standard(hda_csr_t A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, hda_csr_t *P);
 /* hypre_BoomerAMGBuildCoarseOperator (P^T A P) */
 int hda_rap(hda_csr_t A, hda_csr_t P, hda_csr_t *Ac);
+/* approximate ideal restriction (restriction_type air_1 / air_2) for the splitting cf (> 0 C, < 0 F) of the square
+ * operator A: R (C points x rows), built on the device.  distance 1 or 2; strong_th / filter_th >= 0.  stats: [0] rows that fell
+ * back to injection, [1] the largest neighbourhood, [2..4] C rows solved by the small (m <= 32), mid (m <= 88) and large tier */
+int hda_air_restriction(hda_csr_t A, const int *cf, int distance, double strong_th, double filter_th, hda_csr_t *R, int64_t stats[5]);
 /* aggressive coarsening, stage by stage (HYPRE_BoomerAMGSetAggNumLevels / SetNumPaths / SetAggInterpType 4; hypre_BoomerAMGCreate2ndS,
  * second PMIS pass, hypre_BoomerAMGBuildMultipass): S2 = strong connections of distance <= 2 among the C points of cf (values = number
  * of paths); the second pass updates cf in place; multipass P for a given splitting */
