@@ -72,7 +72,8 @@ class MgrLevelParams(C.Structure):
                 ("coarse_ilu_max_iter", C.c_int), ("coarse_ilu_tri_solve", C.c_int), ("coarse_ilu_lower_it", C.c_int), ("coarse_ilu_upper_it", C.c_int),
                 ("frelax_krylov", C.c_int), ("frelax_krylov_precond", C.c_int), ("frelax_kp", KrylovParams),
                 ("coarse_krylov", C.c_int), ("coarse_krylov_precond", C.c_int), ("coarse_kp", KrylovParams),
-                ("mgr_cycle", C.c_int), ("mgr_frelax_pos", C.c_int), ("mgr_gsmooth_pos", C.c_int), ("grelax_blocks", C.c_int)]
+                ("mgr_cycle", C.c_int), ("mgr_frelax_pos", C.c_int), ("mgr_gsmooth_pos", C.c_int), ("grelax_blocks", C.c_int),
+                ("coarse_type", C.c_int), ("nonglk_max_elmts", C.c_int), ("coarse_th", C.c_double)]
 
 
 # every symbol include/hypredrv_amd.h declares (checked by tests/test_cabi_symbols.py)
@@ -84,7 +85,7 @@ SYMBOLS = [
     "hda_spgemm", "hda_amg_create", "hda_amg_destroy", "hda_amg_num_levels",
     "hda_last_precond_calls", "hda_amg_create_dof", "hda_format_bytes", "hda_probe_spmv", "hda_probe_read", "hda_amg_level_matrix", "hda_amg_level_cf", "hda_amg_complexities", "hda_amg_vcycle_bytes",
     "hda_amg_vcycle", "hda_pcg", "hda_gmres", "hda_time_kernel", "hda_solve_device",
-    "hda_pcg_iteration_bytes", "hda_memory_stats", "hda_memory_cached", "hda_memory_driver_stats", "hda_memory_trim", "hda_comm_selftest", "hda_check_row_total", "hda_ilu_create", "hda_ilu_create_blocks", "hda_ilu_blocks", "hda_ilu_factors", "hda_fgmres", "hda_bicgstab", "hda_mgr_create", "hda_mgr_matrix",
+    "hda_pcg_iteration_bytes", "hda_memory_stats", "hda_memory_cached", "hda_memory_driver_stats", "hda_memory_trim", "hda_comm_selftest", "hda_check_row_total", "hda_ilu_create", "hda_ilu_create_blocks", "hda_ilu_blocks", "hda_ilu_factors", "hda_fgmres", "hda_bicgstab", "hda_mgr_create", "hda_mgr_matrix", "hda_mgr_blk_inverses",
     "hda_probe_add", "hda_probe_read_id", "hda_borrow_hypredrv", "hda_comm_stats", "hda_comm_name", "hda_comm_size", "hda_halo_plan_host",
     "hda_amd_partitioned_levels", "hda_amd_hierarchy_levels",
     "hda_second_strength", "hda_coarsen_second_pass", "hda_interp_multipass", "hda_truncate_rows",
@@ -171,6 +172,7 @@ def load():
     L.hda_amg_destroy.argtypes = [vp]
     L.hda_mgr_create.argtypes = [vp, ip, C.c_int, P(MgrLevelParams), P(AmgParams), C.c_int, P(vp)]
     L.hda_mgr_matrix.argtypes = [vp, C.c_int, C.c_int, P(vp)]
+    L.hda_mgr_blk_inverses.argtypes = [vp, C.c_int, C.c_int, P(C.c_double), P(C.c_int), P(C.c_int)]
     L.hda_ilu_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, P(vp)]
     L.hda_ilu_factors.argtypes = [vp, C.c_int, P(vp)]
     L.hda_ilu_create_blocks.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int64), P(vp)]
@@ -490,7 +492,8 @@ class Amg:
         return x
 
 
-MGR_INTERP = {"injection": 0, "l1-jacobi": 1, "jacobi": 2}
+MGR_INTERP = {"injection": 0, "l1-jacobi": 1, "jacobi": 2, "blk-jacobi": 12}
+MGR_COARSE = {"rap": 0, "galerkin": 0, "non-galerkin": 1}
 MGR_RESTRICT = {"injection": 0, "jacobi": 2, "columped": 14}
 MGR_FRELAX = {"jacobi": 7, "single": 7, "l1-jacobi": 18, "amg": 2, "ilu": 32}
 MGR_GRELAX = {"none": -1, "h-fgs": 3, "h-bgs": 4, "h-ssor": 6, "l1-hfgs": 13, "l1-hbgs": 14, "l1-hsgs": 88, "ilu": 16}
@@ -539,6 +542,9 @@ class Mgr:
             arr[k].frelax_sweeps = lv.get("f_sweeps", 1)
             arr[k].grelax_type = MGR_GRELAX[lv.get("g_relaxation", "none")]
             arr[k].grelax_sweeps = lv.get("g_sweeps", 1)
+            arr[k].coarse_type = MGR_COARSE[lv.get("coarse_level_type", "rap")]
+            arr[k].nonglk_max_elmts = lv.get("nonglk_max_elmts", 1)   # hypre's default (non-galerkin only)
+            arr[k].coarse_th = lv.get("coarse_th", 0.0)
             arr[k].grelax_blocks = lv.get("g_blocks", 1)   # row blocks of the hybrid Gauss-Seidel global relaxation (the reference at np = V)
             if lv.get("f_amg") is not None:   # AmgParams of 'f_relaxation: {amg: {...}}'
                 self._keep.append(lv["f_amg"])
@@ -563,6 +569,17 @@ class Mgr:
         out = C.c_void_p()
         _check(load().hda_mgr_matrix(self.h, level, which, C.byref(out)))
         return Csr(out, owned=False, keep=self)
+
+    def block_inverses(self, level, tier=0):
+        """F-block inverses of a reduction level as an array (nblk, b, b), and nf (the short last block: its top-left corner)"""
+        b, nf = C.c_int(), C.c_int()
+        _check(load().hda_mgr_blk_inverses(self.h, level, tier, None, C.byref(b), C.byref(nf)))
+        if b.value == 0:
+            return np.zeros((0, 0, 0)), 0
+        nblk = -(-nf.value // b.value)
+        out = np.zeros(nblk * b.value * b.value)
+        _check(load().hda_mgr_blk_inverses(self.h, level, tier, _dp(out), C.byref(b), C.byref(nf)))
+        return out.reshape(nblk, b.value, b.value), nf.value
 
     def vcycle(self, b):
         b = np.ascontiguousarray(b, dtype=np.float64)

@@ -6,6 +6,7 @@
 #include "hda_dist.h"
 #include "hda_kernels.h"
 
+#include <chrono> // (Mgr::level_ms, timed in hda_mgr.hip)
 #include <memory>
 #include <vector>
 
@@ -342,9 +343,11 @@ struct NestedKrylov { // the subset of KrylovParams a nested solve uses (hda_kry
 };
 struct MgrLevelParams {
    std::vector<int> f_labels;          // level.N.f_dofs
-   int interp_type = 0;                // prolongation_type: 0 injection, 1 l1-jacobi, 2 jacobi
+   int interp_type = 0;                // prolongation_type: 0 injection, 1 l1-jacobi, 2 jacobi, 12 blk-jacobi
    int restrict_type = 0;              // restriction_type: 0 injection, 2 jacobi, 14 columped
-   int coarse_type = 0;                // coarse_level_type: 0 rap
+   int coarse_type = 0;                // coarse_level_type: 0 rap, 1 non-galerkin (A_CC + Ahat_CF W_B)
+   int nonglk_max_elmts = 1;           // non-galerkin: entries kept per row of A_CF (largest magnitudes; 0 = all; mgr.c:1311)
+   double coarse_th = 0.0;             // coarse_th: drop |a_ij| < coarse_th max_k |a_ik| off the diagonal of the reduced operator
    int frelax_type = 7, frelax_sweeps = 1;   // f_relaxation: 7 jacobi, 18 l1-jacobi, 2 amg (one BoomerAMG cycle on A_FF), 32 ilu (ILU(0) of A_FF)
    AmgParams frelax_amg;                     // f_relaxation.amg block
    IluParams ilu;                            // ILU arguments of this level's ILU components (f_relaxation 32, g_relaxation 16)
@@ -369,7 +372,26 @@ struct MgrParams {
    int                         ckrylov_method = -1;
    NestedKrylov                ckrylov;
    bool                        ckrylov_precond = true;
+   bool                        keep_blocks = false; // keep the F-block inverses after setup (the test entry hda_mgr_blk_inverses reads them)
 };
+// F blocks of an MGR level (hda_mgr_blk.hip): the owned F points in local order cut into groups of b, the
+// inverses of the diagonal blocks of A_FF on them (block k at inv + k b^2, row-major with row stride b)
+constexpr int kMgrBlkMax = 32;
+struct MgrBlocks {
+   int            b = 0, nf = 0, nblk = 0;
+   DArray<int>    fidx, frow; // owned row -> F index (n + 1 entries, an exclusive scan); F index -> owned row
+   DArray<double> inv;
+};
+// tier 0: by b (b <= 8 the small tier, else the large one); 1 / 2 force a tier.  row0: global id of the first owned row.
+void mgr_blk_build(const DCsr &A, const int *cf, int b, int level, long long row0, int tier, MgrBlocks &B);
+void mgr_blk_invert(const DCsr &A, const int *cf, int level, long long row0, int tier, MgrBlocks &B);
+// P = [W; I], W = -B^-1 A_FC with the union pattern of each block
+void mgr_blk_prolongation(const DCsr &A, const int *cf, const int *cidx, int ncols, const MgrBlocks &B, DCsr &P);
+// the C rows of A (fine columns): C entries whole, F entries cut to the kmax largest magnitudes (gids: global column ids)
+void mgr_nongalerkin_rows(const DCsr &A, const int *cf, const int *cidx, int nc, const std::vector<long long> &gids, int kmax, DCsr &M);
+// coarse_th drop in place; ghosts (may be null): the ghost list of A's columns, compacted to the columns still used
+void mgr_coarse_drop(DCsr &A, double th, std::vector<long long> *ghosts);
+
 class Mgr {
  public:
    explicit Mgr(const MgrParams &p) : prm(p) {}
@@ -383,6 +405,12 @@ class Mgr {
    void        rebind(const DCsr &A, const HaloPlan *hA);
    int         num_reduction_levels() const { return (int)lv.size(); }
    const DCsr &matrix(int level, int which) const; // which 0 operator (level == reduction levels: coarsest), 1 P, 2 R
+   // F-block inverses of a reduction level (empty when the level builds none); tier 1 / 2 recomputes them with that kernel tier
+   std::vector<double> block_inverses(int level, int tier, int &b, int &nf);
+   // row-partition view of a level's operator (which 0; level == reduction levels: the coarsest) or P (which 1): the first owned row,
+   // the first owned column and the global ids of the ghost columns
+   void                dist_view(int level, int which, long long &row0, long long &col0, std::vector<long long> &ghosts) const;
+   std::vector<double> level_ms; // host wall time of the setup of every reduction level, then of the coarsest solver (ms, device synced)
    size_t      vec_len0() const { return lv.empty() ? 0 : (size_t)std::max(lv[0].A->ncols, lv[0].n); }
    MgrParams   prm;
 
@@ -407,6 +435,9 @@ class Mgr {
       std::unique_ptr<Ilu>   filu; // f_relaxation ilu
       DArray<double>         rF, eF;
       int                    nf = 0;
+      MgrBlocks              blk; // prolongation blk-jacobi / coarse non-galerkin (kept after setup only with MgrParams::keep_blocks)
+      long long              row0 = 0, c0 = 0;          // global ids of the first owned row and the first owned coarse column
+      std::vector<long long> aghosts, pghosts;          // global ids of the ghost columns of A and of P
       int            n = 0, nc = 0;
    };
    double *cycle(int l, const double *f, double *u, bool zero);

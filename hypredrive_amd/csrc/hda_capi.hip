@@ -704,6 +704,7 @@ extern "C" int hda_mgr_create(hda_csr_t A, const int *labels, int nlevels, const
       q.frelax_type = levels[l].frelax_type; q.frelax_sweeps = levels[l].frelax_sweeps;
       q.grelax_type = levels[l].grelax_type; q.grelax_sweeps = levels[l].grelax_sweeps;
       q.grelax_blocks = levels[l].grelax_blocks;
+      q.coarse_type = levels[l].coarse_type; q.nonglk_max_elmts = levels[l].nonglk_max_elmts; q.coarse_th = levels[l].coarse_th;
       if (levels[l].frelax_amg) q.frelax_amg = to_params(levels[l].frelax_amg);
       q.ilu.tri_solve = levels[l].ilu_tri_solve; q.ilu.lower_it = levels[l].ilu_lower_it; q.ilu.upper_it = levels[l].ilu_upper_it;
       auto nested = [](const hda_krylov_params &k) {
@@ -733,6 +734,7 @@ extern "C" int hda_mgr_create(hda_csr_t A, const int *labels, int nlevels, const
    }
    auto h = std::make_unique<hda_amg_s>();
    h->A   = A;
+   p.keep_blocks = true; // (this handle serves the test entry hda_mgr_blk_inverses)
    h->mgr = std::make_unique<Mgr>(p);
    h->mgr->setup(A->get(), std::vector<int>(labels, labels + A->get().nrows));
    *out = h.release();
@@ -748,6 +750,24 @@ extern "C" int hda_mgr_matrix(hda_amg_t h, int level, int which, hda_csr_t *out)
    v->ref      = &h->mgr->matrix(level, which);
    *out        = v.get();
    h->views.push_back(std::move(v));
+   HDA_CATCH
+}
+extern "C" int hda_mgr_blk_inverses(hda_amg_t h, int level, int tier, double *out, int *b, int *nf)
+{
+   HDA_TRY
+   HDA_REQUIRE(h && h->mgr && b && nf, "not an MGR handle");
+   const std::vector<double> v = h->mgr->block_inverses(level, tier, *b, *nf);
+   if (out && !v.empty()) std::copy(v.begin(), v.end(), out);
+   HDA_CATCH
+}
+// host wall time of an MGR setup per reduction level, then of the coarsest solver (tools/mgr_blk_setup.py); *n in: capacity, out: count
+extern "C" int hda_mgr_setup_ms(hda_amg_t h, double *out, int *n)
+{
+   HDA_TRY
+   HDA_REQUIRE(h && h->mgr && n, "not an MGR handle");
+   const std::vector<double> &v = h->mgr->level_ms;
+   if (out) std::copy(v.begin(), v.begin() + std::min<size_t>(v.size(), (size_t)std::max(*n, 0)), out);
+   *n = (int)v.size();
    HDA_CATCH
 }
 // factors (strict lower part L with unit diagonal, rest U) of the stand-alone handle (level < 0) or of

@@ -86,6 +86,7 @@ struct hypre_Solver_struct {
    std::unique_ptr<hda::Mgr>     mgr;
    int                           mgr_block_size = 0, mgr_levels = 0, mgr_max_iter = 1, mgr_cycle = 1, mgr_frelax_cycle = 1, mgr_gsmooth_cycle = 1;
    double                        mgr_coarse_th = 0.0;
+   int                           mgr_nonglk_max_elmts = 1; // HYPRE_MGRSetNonGalerkinMaxElmts (hypre's default 1)
    std::vector<std::vector<int>> mgr_c_labels; // C labels of every reduction level
    const HYPRE_Int              *mgr_marker = nullptr; // borrowed until Setup, as in hypre
    std::vector<int>              mgr_frelax, mgr_fsweeps, mgr_interp, mgr_restrict, mgr_coarse_method, mgr_gsmooth, mgr_giters;

@@ -1533,7 +1533,7 @@ HY_MGR_LEVEL_ARRAY(HYPRE_MGRSetLevelSmoothType, mgr_gsmooth)
 HY_MGR_LEVEL_ARRAY(HYPRE_MGRSetLevelSmoothIters, mgr_giters)
 HY_SETTER(HYPRE_MGRSetNonCpointsToFpoints, HYPRE_Int, (void)v) // every label is either C or F here
 HY_SETTER(HYPRE_MGRSetPMaxElmts, HYPRE_Int, (void)v)           // truncation of the classical-modified interpolation only
-HY_SETTER(HYPRE_MGRSetNonGalerkinMaxElmts, HYPRE_Int, (void)v) // non-Galerkin coarse grids only
+HY_SETTER(HYPRE_MGRSetNonGalerkinMaxElmts, HYPRE_Int, s->mgr_nonglk_max_elmts = v) // non-Galerkin coarse grids only
 HY_SETTER(HYPRE_MGRSetMaxIter, HYPRE_Int, s->mgr_max_iter = v)
 HY_SETTER(HYPRE_MGRSetTol, HYPRE_Real, s->ap.tol = v)
 HY_SETTER(HYPRE_MGRSetPrintLevel, HYPRE_Int, s->ap.print_level = v)
@@ -1575,7 +1575,6 @@ extern "C" HYPRE_Int HYPRE_MGRSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_
    HDA_REQUIRE(s->mgr_cycle == 1 || s->mgr_cycle == 2, "MGR cycle type: 1 (V) or 2 (W)");
    HDA_REQUIRE(s->mgr_frelax_cycle >= 1 && s->mgr_frelax_cycle <= 3 && s->mgr_gsmooth_cycle >= 1 && s->mgr_gsmooth_cycle <= 3,
                "MGR smoothing position: 1 (pre), 2 (post) or 3 (both)");
-   HDA_REQUIRE(s->mgr_coarse_th == 0.0, "MGR: coarse_th (coarse grid truncation) is not implemented");
    // a Krylov handle as component solver (the reference's nested Krylov wrapper, src/internal/krylov.c): its parameters and the
    // BoomerAMG / ILU handle installed as its preconditioner
    auto krylov_method = [](HYPRE_Solver q) {
@@ -1640,6 +1639,8 @@ extern "C" HYPRE_Int HYPRE_MGRSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_
       q.interp_type   = at(s->mgr_interp, l, 0);
       q.restrict_type = at(s->mgr_restrict, l, 0);
       q.coarse_type   = at(s->mgr_coarse_method, l, 0);
+      q.nonglk_max_elmts = s->mgr_nonglk_max_elmts;
+      q.coarse_th        = s->mgr_coarse_th;
       q.frelax_type   = at(s->mgr_frelax, l, 7);
       {
          HYPRE_Solver fk = (size_t)l < s->mgr_fsolver.size() ? s->mgr_fsolver[(size_t)l] : nullptr;
@@ -1659,7 +1660,11 @@ extern "C" HYPRE_Int HYPRE_MGRSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_
          HYPRE_Solver fs = (size_t)l < s->mgr_fsolver.size() ? s->mgr_fsolver[(size_t)l] : nullptr;
          if (krylov_method(fs) >= 0) fs = precond_of(fs);
          HDA_REQUIRE(!fs || fs->kind == (q.frelax_type == 2 ? HDA_SOLVER_AMG : HDA_SOLVER_ILU), "MGR f_relaxation: the F-solver handle does not match its type (amg / ilu)");
-         if (fs && q.frelax_type == 2) { q.frelax_amg = fs->ap; q.frelax_amg.num_functions = std::max(fs->num_functions, 1); }
+         if (fs && q.frelax_type == 2)
+         {
+            HDA_REQUIRE(fs->filter_functions == 0 || fs->num_functions <= 1, "coarsening.filter_functions is not implemented for systems AMG");
+            q.frelax_amg = fs->ap; q.frelax_amg.num_functions = std::max(fs->num_functions, 1);
+         }
          if (fs && q.frelax_type == 32)
          {
             HDA_REQUIRE(ilu_ok(fs), "MGR f_relaxation ilu: only type bj-iluk with fill_level 0 and reordering 0 is implemented");

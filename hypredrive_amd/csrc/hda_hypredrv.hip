@@ -2424,3 +2424,26 @@ extern "C" uint32_t HYPREDRV_LinearSolverGetConverged(HYPREDRV_t h, int *c) { CH
 extern "C" uint32_t HYPREDRV_LinearSolverGetFinalRelativeResidualNorm(HYPREDRV_t h, double *n) { CHECK_INIT_OBJ(h); if (n) *n = h->last_rel; return g_err; }
 extern "C" uint32_t HYPREDRV_LinearSolverGetSetupTime(HYPREDRV_t h, double *s) { CHECK_INIT_OBJ(h); if (s) *s = h->stats.cur().prec; return g_err; }
 extern "C" uint32_t HYPREDRV_LinearSolverGetSolveTime(HYPREDRV_t h, double *s) { CHECK_INIT_OBJ(h); if (s) *s = h->last_solve_s; return g_err; }
+
+// this rank's block of an MGR operator (which 0; level == reduction levels: the coarsest) or P (which 1) after Setup (thread-rank
+// tests): info = {rows, columns, nonzeros, ghost columns, first owned row, first owned column}; arrays may be null (sizes only)
+extern "C" int hda_amd_mgr_view(void *obj, int level, int which, long long *info, int *rowptr, int *col, double *val, long long *ghosts)
+{
+   hypredrv_struct *h = (hypredrv_struct *)obj;
+   if (!h || !h->precon || !h->precon_is_setup || !h->precon->mgr || !info) return 1;
+   try
+   {
+      const Mgr             &M = *h->precon->mgr;
+      const DCsr            &X = M.matrix(level, which);
+      long long              r0 = 0, c0 = 0;
+      std::vector<long long> g;
+      M.dist_view(level, which, r0, c0, g);
+      info[0] = X.nrows; info[1] = X.ncols; info[2] = X.nnz; info[3] = (long long)g.size(); info[4] = r0; info[5] = c0;
+      if (rowptr) X.rowptr.download(rowptr, (size_t)X.nrows + 1);
+      if (col) X.col.download(col, (size_t)X.nnz);
+      if (val) X.val.download(val, (size_t)X.nnz);
+      if (ghosts) std::copy(g.begin(), g.end(), ghosts);
+      return 0;
+   }
+   catch (...) { return 1; }
+}

@@ -241,18 +241,20 @@ void Mgr::setup_dist(const DCsr &A0, const HaloPlan &hA0, const std::vector<long
    std::vector<long long>  part = part0, ghosts = ghosts0;
    DArray<int>             labels;
    labels.upload(labels0.data(), std::max<size_t>(labels0.size(), 1));
+   level_ms.assign(prm.levels.size() + 1, 0.0);
    for (size_t l = 0; l < prm.levels.size(); l++)
    {
+      const auto            t0 = std::chrono::steady_clock::now();
       const MgrLevelParams &p = prm.levels[l];
       Level                &L = lv[l];
-      HDA_REQUIRE(p.interp_type == 0 || p.interp_type == 1 || p.interp_type == 2,
-                  "MGR prolongation_type: injection, jacobi and l1-jacobi are implemented");
+      HDA_REQUIRE(p.interp_type == 0 || p.interp_type == 1 || p.interp_type == 2 || p.interp_type == 12,
+                  "MGR prolongation_type: injection, jacobi, l1-jacobi and blk-jacobi are implemented");
       HDA_REQUIRE(p.restrict_type == 0 || p.restrict_type == 2 || p.restrict_type == 14,
                   "MGR restriction_type: injection, jacobi and columped are implemented");
-      HDA_REQUIRE(p.coarse_type == 0, "MGR coarse_level_type: only rap (Galerkin) is implemented");
+      HDA_REQUIRE(p.coarse_type == 0 || p.coarse_type == 1, "MGR coarse_level_type: rap (Galerkin) and non-galerkin are implemented");
+      HDA_REQUIRE(p.coarse_th >= 0.0, "MGR coarse_th must not be negative");
       HDA_REQUIRE(p.frelax_type == 7 || p.frelax_type == 18 || p.frelax_type == 2 || p.frelax_type == 32,
                   "MGR f_relaxation: jacobi (single), l1-jacobi, amg and ilu are implemented");
-      HDA_REQUIRE(p.frelax_type != 2 || p.frelax_amg.num_functions <= 1, "MGR f_relaxation amg: systems AMG (num_functions > 1) on A_FF is not implemented");
       HDA_REQUIRE(p.grelax_type < 0 || gs_type(p.grelax_type) || p.grelax_type == 16,
                   "MGR g_relaxation: none, the hybrid (l1) Gauss-Seidel types and ilu are implemented");
       HDA_REQUIRE(!p.f_labels.empty(), "MGR: a reduction level without f_dofs");
@@ -288,6 +290,8 @@ void Mgr::setup_dist(const DCsr &A0, const HaloPlan &hA0, const std::vector<long
          Context::get().sync();
       }
       L.nc = nc;
+      L.row0 = part[(size_t)cm.rank];
+      L.aghosts = ghosts;
       // coarse row starts of every rank, global coarse ids of the ghost C points
       std::vector<long long> cpart((size_t)cm.size + 1, 0);
       {
@@ -316,6 +320,8 @@ void Mgr::setup_dist(const DCsr &A0, const HaloPlan &hA0, const std::vector<long
             if (hcf[(size_t)g] > 0) pghosts.push_back((long long)hg[(size_t)g]);
          HDA_REQUIRE((int)pghosts.size() == ncx, "MGR: ghost coarse numbering is inconsistent");
       }
+      L.c0      = cpart[(size_t)cm.rank];
+      L.pghosts = pghosts;
       // row statistics of the F rows (ghost F columns see their owners' values), column sums of A_FF
       DArray<double> dF((size_t)std::max(nx, 1)), l1F((size_t)std::max(nx, 1)), l1all((size_t)std::max(nx, 1)), csum;
       dF.zero();
@@ -338,7 +344,22 @@ void Mgr::setup_dist(const DCsr &A0, const HaloPlan &hA0, const std::vector<long
       }
       L.dinvF.alloc((size_t)std::max(n, 1));
       if (n) k_mgr_dinvF<<<ceil_div(n, 256), 256, 0, STREAM>>>(n, L.cf.data(), p.frelax_type == 18 ? l1all.data() : dF.data(), L.dinvF.data());
+      // F blocks and their inverses (prolongation blk-jacobi, coarse non-galerkin); W_B built once when P is blk-jacobi
+      const bool need_blk = p.interp_type == 12 || p.coarse_type == 1;
+      DCsr       PB; // P_B = [W_B; I] of a non-Galerkin level whose P is not blk-jacobi
+      L.blk = MgrBlocks();
+      if (need_blk)
+      {
+         mgr_blk_build(*A, L.cf.data(), (int)p.f_labels.size(), (int)l, L.row0, 0, L.blk);
+         if (p.interp_type != 12) mgr_blk_prolongation(*A, L.cf.data(), L.cidx.data(), nc + ncx, L.blk, PB);
+      }
       // P (columns [owned coarse | ghost coarse])
+      if (p.interp_type == 12)
+      {
+         mgr_blk_prolongation(*A, L.cf.data(), L.cidx.data(), nc + ncx, L.blk, L.P);
+         if (multi) L.hP = make_halo_plan(nc, cpart, pghosts);
+      }
+      else
       {
          DArray<int> cnt((size_t)n + 1);
          cnt.zero();
@@ -430,7 +451,8 @@ void Mgr::setup_dist(const DCsr &A0, const HaloPlan &hA0, const std::vector<long
             {
                L.hFF = make_halo_plan(nf, L.fpart, L.fghosts);
                const char *mode = getenv("HDA_DIST_SETUP");
-               if ((mode && !strcmp(mode, "replicated")) || fp.coarsen_type != 8) L.famg->setup_dist(L.Aff, L.hFF, L.fpart, L.fghosts);
+               L.famg->dof_row_offset = L.fpart[(size_t)cm.rank]; // systems AMG: function = global A_FF index mod num_functions
+               if ((mode && !strcmp(mode, "replicated")) || fp.coarsen_type != 8 || fp.num_functions > 1) L.famg->setup_dist(L.Aff, L.hFF, L.fpart, L.fghosts);
                else L.famg->setup_dist_partitioned(L.Aff, L.hFF, L.fpart, L.fghosts);
             }
             else L.famg->setup(L.Aff);
@@ -481,7 +503,18 @@ void Mgr::setup_dist(const DCsr &A0, const HaloPlan &hA0, const std::vector<long
       Level                  *next = (l + 1 < prm.levels.size()) ? &lv[l + 1] : nullptr;
       DCsr                   &Anext = next ? next->A_own : Ac;
       std::vector<long long>  cghosts;
-      if (multi)
+      if (p.coarse_type == 1)
+      { // non-Galerkin: A_c = A_CC + Ahat_CF W_B = M P_B (M: the C rows of A with their F entries cut)
+         std::vector<long long> gids((size_t)std::max(nx, 1));
+         for (int j = 0; j < n; j++) gids[(size_t)j] = L.row0 + j;
+         for (int g = 0; g < ng; g++) gids[(size_t)(n + g)] = ghosts[(size_t)g];
+         DCsr        M;
+         const DCsr &PBr = p.interp_type == 12 ? L.P : PB;
+         mgr_nongalerkin_rows(*A, L.cf.data(), L.cidx.data(), nc, gids, p.nonglk_max_elmts, M);
+         if (multi) dist_spgemm(M, *hA, PBr, pghosts, cpart, Anext, cghosts);
+         else spgemm(M, PBr, Anext);
+      }
+      else if (multi)
       {
          DCsr                   AP;
          std::vector<long long> apg;
@@ -494,6 +527,7 @@ void Mgr::setup_dist(const DCsr &A0, const HaloPlan &hA0, const std::vector<long
          spgemm(*A, L.P, AP);
          spgemm(L.R, AP, Anext);
       }
+      if (p.coarse_th > 0.0) mgr_coarse_drop(Anext, p.coarse_th, multi ? &cghosts : nullptr);
       DArray<int> lc((size_t)std::max(nc, 1));
       if (n) k_mgr_coarse_labels<<<ceil_div(n, 256), 256, 0, STREAM>>>(n, L.cf.data(), L.cidx.data(), L.labels.data(), lc.data());
       Context::get().sync();
@@ -510,12 +544,17 @@ void Mgr::setup_dist(const DCsr &A0, const HaloPlan &hA0, const std::vector<long
       spmv_prepare(*A);
       spmv_prepare(L.P);
       spmv_prepare(L.R);
+      if (!prm.keep_blocks) L.blk = MgrBlocks(); // P and A_c are built: the inverses are only kept for the test entry
       labels = std::move(lc);
       A      = &Anext;
       hA     = &hnext;
       part   = cpart;
       ghosts = cghosts;
+      Context::get().sync();
+      level_ms[l] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
    }
+   const auto tc = std::chrono::steady_clock::now();
+   auto coarse_time = [&] { level_ms.back() = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc).count(); };
    cparts  = part;
    cghosts_ = ghosts;
    // coarsest system: BoomerAMG, or block-Jacobi ILU(0) iterations
@@ -528,6 +567,7 @@ void Mgr::setup_dist(const DCsr &A0, const HaloPlan &hA0, const std::vector<long
       fc.alloc(clen);
       uc.alloc(clen);
       Context::get().sync();
+      coarse_time();
       return;
    }
    cilu.reset();
@@ -543,6 +583,44 @@ void Mgr::setup_dist(const DCsr &A0, const HaloPlan &hA0, const std::vector<long
    fc.alloc(clen);
    uc.alloc(clen);
    Context::get().sync();
+   coarse_time();
+}
+
+void Mgr::dist_view(int level, int which, long long &row0, long long &col0, std::vector<long long> &ghosts) const
+{
+   HDA_REQUIRE(level >= 0 && level <= (int)lv.size() && (which == 0 || which == 1) && !(which == 1 && level == (int)lv.size()), "MGR view out of range");
+   if (level == (int)lv.size())
+   {
+      row0 = col0 = cparts[(size_t)Comm::world().rank];
+      ghosts = cghosts_;
+      return;
+   }
+   const Level &L = lv[(size_t)level];
+   row0   = L.row0;
+   col0   = which == 0 ? L.row0 : L.c0;
+   ghosts = which == 0 ? L.aghosts : L.pghosts;
+}
+
+std::vector<double> Mgr::block_inverses(int level, int tier, int &b, int &nf)
+{
+   HDA_REQUIRE(level >= 0 && level < (int)lv.size(), "MGR level out of range");
+   HDA_REQUIRE(tier >= 0 && tier <= 2, "MGR block inverses: tier 0 (the setup's), 1 (b <= 8) or 2");
+   Level &L = lv[(size_t)level];
+   b        = L.blk.b;
+   nf       = L.blk.nf;
+   HDA_REQUIRE(b > 0 || prm.keep_blocks || (prm.levels[(size_t)level].interp_type != 12 && prm.levels[(size_t)level].coarse_type != 1),
+               "MGR block inverses: this handle did not keep them (MgrParams::keep_blocks)");
+   if (b == 0) return {};
+   if (tier > 0)
+   {
+      MgrBlocks T;
+      T.b = L.blk.b; T.nf = L.blk.nf; T.nblk = L.blk.nblk;
+      T.fidx.copy_from(L.blk.fidx);
+      T.frow.copy_from(L.blk.frow);
+      mgr_blk_invert(*L.A, L.cf.data(), level, L.row0, tier, T);
+      return T.inv.to_host();
+   }
+   return L.blk.inv.to_host();
 }
 
 void Mgr::rebind(const DCsr &A, const HaloPlan *hA)

@@ -196,6 +196,11 @@ typedef struct {
    /* row blocks of the hybrid Gauss-Seidel global relaxation (g_relaxation 3/4/6/13/14/88) = the reference at np = V (as hda_amg_params.blocks):
     * 1 = one block (the sequential sweep), V > 1 = hypre's even split of the level's rows, 0 = the setup's choice (one block up to 100 000 rows) */
    int               grelax_blocks;
+   /* coarse_level_type: 0 rap (Galerkin), 1 non-galerkin (A_CC + Ahat_CF W_B, Ahat_CF = A_CF cut to nonglk_max_elmts entries per row, 0 = all;
+    * W_B = -B^-1 A_FC with B the block diagonal of A_FF, blocks of n_f_labels consecutive F points).  coarse_th > 0: off-diagonal entries of
+    * the reduced operator with |a_ij| < coarse_th max_k |a_ik| are dropped.  interp_type 12 (blk-jacobi) is P = [W_B; I]. */
+   int               coarse_type, nonglk_max_elmts;
+   double            coarse_th;
 } hda_mgr_level_params;
 int hda_mgr_create(hda_csr_t A, const int *labels, int nlevels, const hda_mgr_level_params *levels,
                    const hda_amg_params *coarsest_amg, int max_iter, hda_amg_t *out);
@@ -204,6 +209,10 @@ int hda_mgr_matrix(hda_amg_t h, int level, int which, hda_csr_t *out);
 /* borrowed view of the factors: strict lower part = L (unit diagonal), rest = U.  level < 0: the handle of
  * hda_ilu_create; level >= 0: the complex smoother of that AMG level. */
 int hda_ilu_factors(hda_amg_t h, int level, hda_csr_t *out);
+/* F-block inverses of an MGR reduction level (blk-jacobi / non-galerkin): *b = block size, *nf = owned F points; out (may be NULL) gets
+ * ceil(nf / b) blocks of b * b doubles, row-major with row stride b (a short last block fills its top-left corner, the rest 0).
+ * tier 0: the setup's inverses; 1 (b <= 8) / 2: recomputed by that kernel tier.  *b = 0: the level built no blocks. */
+int hda_mgr_blk_inverses(hda_amg_t h, int level, int tier, double *out, int *b, int *nf);
 int hda_amg_num_levels(hda_amg_t h);
 /* which: 0 = A_l, 1 = P_l, 2 = R_l; returns a borrowed handle (do not destroy) */
 int hda_amg_level_matrix(hda_amg_t h, int level, int which, hda_csr_t *out);
