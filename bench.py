@@ -14,6 +14,12 @@ keeps the global problem at --grid^3 instead.
 Launch: under torchrun (WORLD_SIZE set) this process is one rank.  `python bench.py --gpus N` with
 N > 1 and no WORLD_SIZE starts the N ranks itself as CHILD processes (reference:
 scripts/node_scaling.sh:1275-1292 `mpirun -np N`), before anything here touches the GPU.
+
+A plain run does what its line needs and nothing more: build the system, set up (cold + warm, as the
+reference's protocol), warm up, time the K steps, write --dump-outputs, print the line.  Everything that
+takes runs of its own -- the CPU baseline, the counter passes, the seam and per-kernel table, the
+plain-CSR / uncoded / cpu_defaults / aggressive / side-config runs, and for N > 1 the strong_<grid> and
+n1_reference child launches -- runs only with --full (a few minutes at 256^3).
 """
 import argparse
 import json
@@ -33,8 +39,8 @@ if ROOT not in sys.path:
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
-# The headline is measured first and published at once (stderr + gpurun_out/bench_headline.json; printed to stdout by the SIGTERM handler
-# if the job is ended during the extras); the extras that follow share ONE time budget and are skipped, by name, once it is spent.
+# --full: the headline is measured first and published at once (stderr + a file, see publish_headline; printed to stdout by the SIGTERM
+# handler if the job is ended during the extras); the extras that follow share ONE time budget and are skipped, by name, once it is spent.
 STATE = {"headline": None, "printed": False, "deadline": None}
 
 
@@ -525,10 +531,11 @@ def run(args):
             out["level0_residual"] = {"kernel": "k_spmv_stream<RESID> on the level-0 operator (plain CSR), inside the ILU(0) smoothing steps",
                                       "avg_ms": ms, "launches": cnt, "csr_bytes_per_launch": bts, "csr_equiv_gbs": gbs(bts, ms),
                                       "csr_equiv_frac": gbs(bts, ms) / HBM_PEAK_GBS}
-        if not args.child:
-            publish_headline(out)
-        if w.size == 1 and not aniso:
-            single_extras(args, out, hh, A, amg, fb0, iters)
+        if args.full:
+            if not args.child:
+                publish_headline(out)
+            if w.size == 1 and not aniso:
+                single_extras(args, out, hh, A, amg, fb0, iters)
     del A, amg
     h.destroy_solver()
     h.close()
@@ -537,7 +544,7 @@ def run(args):
 
 
 def single_extras(args, out, hh, A, amg, fb0, iters):
-    """N = 1 only, after the headline has been published: the CPU baseline (part of the line's contract: first), the counter passes
+    """--full, N = 1 only, after the headline has been published: the CPU baseline (part of the line's contract: first), the counter passes
     behind roofline.traffic and solve_phase_traffic_gb, the same solve through the kernel-level seam, the per-kernel table, the
     plain-CSR / uncoded child runs, the reference's CPU-build defaults (cpu_defaults) and the aggressive-coarsening option.  All of
     them share the budget of publish_headline(); one that does not fit is recorded as skipped, by name."""
@@ -688,7 +695,7 @@ def plain_csr_child(args, window="0"):
     codings are off -- what a variable-coefficient operator of the same sparsity gets with default settings."""
     env = dict(os.environ, HDA_CODED="0", HDA_WINDOW=window)
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--grid", str(args.n), "--no-cpu-baseline", "--no-kernel-table", "--no-plain-csr", "--no-aggressive", "--no-traffic", "--no-cpu-defaults", "--no-side-configs", "--child"]
+           "--grid", str(args.n), "--child"]
     try:
         r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=max(min(300.0, budget_left()), 30.0))
     except subprocess.TimeoutExpired:
@@ -728,8 +735,7 @@ def measure_traffic(args, limit_s=240):
         for ctr, sub in (("FETCH_SIZE", "fetch"), ("WRITE_SIZE", "write")):
             # the program itself after `--`: no env / shell hop between the profiler's preloaded library and python
             cmd = [prof, "--pmc", ctr, "--output-format", "csv", "-d", os.path.join(tmp, sub), "-o", "run", "--",
-                   sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "1", "--warmup", "0", "--grid", str(args.n), "--child",
-                   "--no-cpu-baseline", "--no-kernel-table", "--no-plain-csr", "--no-aggressive", "--no-traffic", "--no-cpu-defaults", "--no-side-configs"]
+                   sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "1", "--warmup", "0", "--grid", str(args.n), "--child"]
             left = limit_s - (time.perf_counter() - t0)
             if left < 20:
                 return None, f"counter passes exceeded {limit_s} s"
@@ -765,7 +771,7 @@ def child_bench(extra, nranks, timeout_s):
     me = os.path.abspath(__file__)
     cmd = [sys.executable, me] if nranks == 1 else [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nranks}",
                                                     "--master-addr", "127.0.0.1", "--master-port", str(free_port()), me]
-    cmd += ["--gpus", str(nranks), "--child", "--no-cpu-baseline", "--no-kernel-table", "--no-plain-csr", "--no-aggressive", "--no-traffic", "--no-cpu-defaults", "--no-side-configs"] + extra
+    cmd += ["--gpus", str(nranks), "--child"] + extra
     try:
         r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout_s)
     except subprocess.TimeoutExpired:
@@ -859,23 +865,26 @@ def main():
                     "--workload aniso); default 256 (lap7) / 128 (aniso)")
     ap.add_argument("--workload", choices=["lap7", "aniso"], default="lap7", help="lap7: BASELINE configs 2 / 3 (the headline metric). aniso: "
                     "BASELINE config 5 stand-in, GMRES + AMG with the ILU(0) smoother on a heterogeneous anisotropic reservoir operator")
-    ap.add_argument("--cpu-sample", type=int, default=0, help="grid size of the CPU-baseline run (default: the benchmark's own --grid; "
+    ap.add_argument("--cpu-sample", type=int, default=0, help="--full: grid size of the CPU-baseline run (default: the benchmark's own --grid; "
                     "256^3 takes about 2 minutes of host time, most of it the oracle's setup)")
     ap.add_argument("--strong", action="store_true", help="N > 1: --grid is the GLOBAL problem, cut into N blocks (fixed-size series). Default is "
                     "weak scaling: --grid is the block of every rank (global grid = block x rank grid; 256 on 8 GPUs = "
-                    "BASELINE config 3, 512^3); the weak line of N > 1 also carries the strong series' point (strong_<grid>) and the "
+                    "BASELINE config 3, 512^3); with --full the weak line of N > 1 also carries the strong series' point (strong_<grid>) and the "
                     "same-node N = 1 point (n1_reference) from child launches")
     ap.add_argument("--weak", action="store_true", help="(default; kept for older command lines)")
+    ap.add_argument("--full", action="store_true", help="after the line's own measurement, run everything else the benchmark measures or "
+                    "checks (CPU baseline, counter passes, seam and kernel table, plain-CSR / uncoded / cpu_defaults / aggressive / "
+                    "side-config runs; N > 1: strong_<grid> and n1_reference) and add it to the line; the --no-* options skip parts of it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-table", action="store_true")
     ap.add_argument("--no-plain-csr", action="store_true")
-    ap.add_argument("--no-aggressive", action="store_true", help="N = 1: skip the side run with one aggressive-coarsening level")
-    ap.add_argument("--no-cpu-defaults", action="store_true", help="N = 1: skip the side run with the reference's CPU-build defaults (HMIS, hybrid l1 Gauss-Seidel)")
-    ap.add_argument("--no-cpu-defaults-oracle", action="store_true", help="cpu_defaults without the oracle's run on the same row blocks (iters_match)")
-    ap.add_argument("--no-side-configs", action="store_true", help="N = 1: skip gmres_amg_ilu0 / gmres_mgr (BASELINE configs 5 and 4 on stand-in data)")
-    ap.add_argument("--no-traffic", action="store_true", help="N = 1, 256^3: skip the two rocprofv3 --pmc passes behind roofline.traffic "
+    ap.add_argument("--no-aggressive", action="store_true", help="--full, N = 1: skip the side run with one aggressive-coarsening level")
+    ap.add_argument("--no-cpu-defaults", action="store_true", help="--full, N = 1: skip the side run with the reference's CPU-build defaults (HMIS, hybrid l1 Gauss-Seidel)")
+    ap.add_argument("--no-cpu-defaults-oracle", action="store_true", help="--full: cpu_defaults without the oracle's run on the same row blocks (iters_match)")
+    ap.add_argument("--no-side-configs", action="store_true", help="--full, N = 1: skip gmres_amg_ilu0 / gmres_mgr (BASELINE configs 5 and 4 on stand-in data)")
+    ap.add_argument("--no-traffic", action="store_true", help="--full, N = 1, 256^3: skip the two rocprofv3 --pmc passes behind roofline.traffic "
                     "(the committed profiles/traffic.json is quoted instead)")
-    ap.add_argument("--no-extras", action="store_true", help="N > 1: skip the strong_<grid> and n1_reference child launches")
+    ap.add_argument("--no-extras", action="store_true", help="--full, N > 1: skip the strong_<grid> and n1_reference child launches")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (solution, sampled "
                     "above 2^21 entries; solver report) as float64 .npy files into DIR")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)  # a launch made by another bench.py: no further children
@@ -909,7 +918,7 @@ def main():
         wd.cancel()  # (the child launches below have limits of their own)
     if out is not None:
         PHASE["name"] = "extras (strong / n1 child launches)"
-        if out["n_gpus"] > 1 and not (args.child or args.no_extras or args.strong or args.workload != "lap7" or out.get("rccl_error")):
+        if args.full and out["n_gpus"] > 1 and not (args.child or args.no_extras or args.strong or args.workload != "lap7" or out.get("rccl_error")):
             try:
                 multi_extras(args, out)
             except Exception as e:  # noqa: BLE001 - the headline is measured: extras must not lose it

@@ -2024,6 +2024,30 @@ def test_bench_reports_the_serial_measurement_when_the_overlapped_phase_hangs():
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["warmup"] == 1 and d["converged"] and d["scaling"] == "weak"
 
 
+BENCH_EXTRAS = ("cpu_baseline", "iters_match", "seam", "kernels", "plain_csr", "uncoded", "cpu_defaults", "cpu_defaults_rank_blocks",
+                "aggressive_1", "gmres_amg_ilu0", "gmres_mgr", "extras_skipped")
+
+
+def test_bench_plain_run_measures_the_line_alone_and_full_adds_the_extras(tmp_path):
+    """A plain bench.py run on one GPU prints the line (headline fields, setup, probes) and runs nothing of its own besides; --full adds the
+    extras (here the CPU baseline, the seam, the kernel table and the aggressive-coarsening run; the slower ones skipped by their options)."""
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--grid", "48", "--steps", "2", "--warmup", "1"]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-traffic", "--no-plain-csr", "--no-cpu-defaults", "--no-side-configs"])):
+        r = subprocess.run(base + extra, capture_output=True, text=True, cwd=str(tmp_path), timeout=300)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        got = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{") and '"metric"' in l]
+        assert len(got) == 1, r.stdout[-2000:]
+        lines[mode] = got[0]
+    p, f = lines["plain"], lines["full"]
+    for d in (p, f):
+        assert d["unit"] == "DOF/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and d["converged"]
+        assert d["value"] == pytest.approx(48 ** 3 / (d["ms_per_step"] * 1e-3)) and d["setup_ms"] > 0 and d["roofline"]["avg_ms"] > 0
+    assert not [k for k in BENCH_EXTRAS if k in p]
+    assert f["iters"] == p["iters"] and f["cpu_baseline"]["iters_match"] and f["seam"]["iters"] == f["iters"]
+    assert set(f["kernels"]) == {"spmv", "l1_jacobi", "residual", "vcycle"} and f["aggressive_1"]["converged"]
+
+
 @pytest.mark.parametrize("what", [0, 1])
 def test_thread_rank_seam_selftests(what):
     """include/hypredrv_amd_testranks.h hda_testranks_selftest, in a child process (what = 1 asks the driver for nearly all of HBM).

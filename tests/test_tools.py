@@ -87,6 +87,26 @@ def test_bench_skips_its_counter_passes_when_it_is_being_profiled(monkeypatch):
     assert t is None and "profiled" in why
 
 
+@pytest.mark.parametrize("full", [False, True])
+def test_bench_starts_its_multi_gpu_child_launches_only_with_full(monkeypatch, capsys, full):
+    """A plain `bench.py --gpus N` rank prints its line and starts nothing more; the strong_<grid> / n1_reference child launches belong to
+    --full.  (The rank's own measurement is stubbed: this is the decision in main(), on the host.)"""
+    import json
+    import sys
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    launched = []
+    monkeypatch.setattr(bench, "run", lambda args: {"metric": "m", "value": 1.0, "n_gpus": 2, "scaling": "weak"})
+    monkeypatch.setattr(bench, "multi_extras", lambda args, out: launched.append(out))
+    monkeypatch.setattr(bench.signal, "signal", lambda *a: None)
+    monkeypatch.setenv("WORLD_SIZE", "2")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--steps", "1"] + (["--full"] if full else []))
+    bench.main()
+    assert len(launched) == (1 if full else 0)
+    assert json.loads(capsys.readouterr().out.strip())["value"] == 1.0
+
+
 def test_series_b_rank_block_numbering_is_the_generators():
     """tools/series_b.py --rank-grid p hands the library the n^3 Laplacian in the numbering the reference's generator produces at
     np = p^3 (`-P p p p`, examples/src/C_laplacian/laplacian.c:504-520 grid2idx; rhs :898-905): the oracle's restatement of that
