@@ -89,7 +89,7 @@ SYMBOLS = [
     "hda_probe_add", "hda_probe_read_id", "hda_borrow_hypredrv", "hda_comm_stats", "hda_comm_name", "hda_comm_size", "hda_halo_plan_host",
     "hda_amd_partitioned_levels", "hda_amd_hierarchy_levels",
     "hda_second_strength", "hda_coarsen_second_pass", "hda_interp_multipass", "hda_truncate_rows",
-    "hda_interp_mm_extpi", "hda_interp_standard", "hda_set_overlap", "hda_marker", "hda_relax_blocks", "hda_l1_norms_blocks", "hda_hmis_blocks", "hda_amg_blocks", "hda_amg_level_blocks",
+    "hda_interp_mm_extpi", "hda_interp_extended", "hda_interp_mm_ext", "hda_interp_one_point", "hda_interp_standard", "hda_set_overlap", "hda_marker", "hda_relax_blocks", "hda_l1_norms_blocks", "hda_hmis_blocks", "hda_amg_blocks", "hda_amg_level_blocks",
     "hda_csr_form", "hda_spmv_mode", "hda_air_restriction",
 ]
 
@@ -160,6 +160,9 @@ def load():
     L.hda_interp_extpi.argtypes = [vp, P(C.c_ubyte), ip, C.c_int, C.c_double, P(vp)]
     L.hda_interp_direct.argtypes = [vp, P(C.c_ubyte), ip, C.c_int, C.c_double, P(vp)]
     L.hda_interp_mm_extpi.argtypes = [vp, P(C.c_ubyte), ip, C.c_int, C.c_double, P(vp)]
+    L.hda_interp_extended.argtypes = [vp, P(C.c_ubyte), ip, C.c_int, C.c_double, P(vp)]
+    L.hda_interp_mm_ext.argtypes = [vp, P(C.c_ubyte), ip, C.c_int, C.c_double, P(vp)]
+    L.hda_interp_one_point.argtypes = [vp, P(C.c_ubyte), ip, P(vp)]
     L.hda_interp_standard.argtypes = [vp, P(C.c_ubyte), ip, C.c_int, C.c_double, P(vp)]
     L.hda_rap.argtypes = [vp, vp, P(vp)]
     L.hda_second_strength.argtypes = [vp, P(C.c_ubyte), ip, C.c_int, P(vp)]
@@ -351,6 +354,30 @@ class Csr:
         cfa = np.ascontiguousarray(np.concatenate([cf, np.zeros(1, np.int32)]), dtype=np.int32)
         out = C.c_void_p()
         _check(load().hda_interp_mm_extpi(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), _ip(cfa), pmax, trunc_factor, C.byref(out)))
+        return Csr(out)
+
+    def interp_extended(self, smask, cf, pmax=4, trunc_factor=0.0):
+        """interpolation type 14 (extended): extended+i without the point itself in its strong F neighbours' denominators"""
+        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
+        cfa = np.ascontiguousarray(np.concatenate([cf, np.zeros(1, np.int32)]), dtype=np.int32)
+        out = C.c_void_p()
+        _check(load().hda_interp_extended(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), _ip(cfa), pmax, trunc_factor, C.byref(out)))
+        return Csr(out)
+
+    def interp_mm_ext(self, smask, cf, pmax=4, trunc_factor=0.0):
+        """interpolation type 16 (mm_extended): mm-ext+i with s_ki := 0"""
+        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
+        cfa = np.ascontiguousarray(np.concatenate([cf, np.zeros(1, np.int32)]), dtype=np.int32)
+        out = C.c_void_p()
+        _check(load().hda_interp_mm_ext(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), _ip(cfa), pmax, trunc_factor, C.byref(out)))
+        return Csr(out)
+
+    def interp_one_point(self, smask, cf):
+        """interpolation type 100 (one_point): weight 1 towards the strong C neighbour of largest |a_ij|"""
+        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
+        cfa = np.ascontiguousarray(np.concatenate([cf, np.zeros(1, np.int32)]), dtype=np.int32)
+        out = C.c_void_p()
+        _check(load().hda_interp_one_point(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), _ip(cfa), C.byref(out)))
         return Csr(out)
 
     def interp_standard(self, smask, cf, pmax=4, trunc_factor=0.0):

@@ -8,6 +8,7 @@
 
 #include <chrono> // (Mgr::level_ms, timed in hda_mgr.hip)
 #include <memory>
+#include <string>
 #include <vector>
 
 namespace hda {
@@ -34,6 +35,7 @@ struct AmgParams {
    int    max_levels      = 25;
    // interpolation (amg.c:120-128)
    int    interp_type  = 6; // extended+i; 17: mm-ext+i, its matrix-matrix form (an operator of its own, one rank); 3: direct with separation of weights (one rank)
+                            // 8: standard; 14: extended; 16: mm-ext; 100: one-point; 4: multipass on ordinary levels (all one rank)
    int    pmax         = 4;
    double trunc_factor = 0.0;
    // relaxation (amg.c:178-199)
@@ -462,7 +464,8 @@ void amg_pmis(const DCsr &A, const unsigned char *smask, uint64_t seed, int leve
 // block, interior C points kept, PMIS from there
 void amg_hmis(const DCsr &A, const unsigned char *smask, const std::vector<int> &part, uint64_t seed, int level, int *cf);
 // hypre_BoomerAMGBuildExtPIInterp (interp_type 6 / 17) or hypre_BoomerAMGBuildDirInterp with separation of weights (3),
-// then InterpTruncation: P (nrows x nc), rows column-sorted.
+// then InterpTruncation: P (nrows x nc), rows column-sorted.  Also standard (8), extended (14), mm-ext (16), one-point (100) and
+// multipass on the given one-pass splitting (4).
 void amg_interp_extpi(const DCsr &A, const unsigned char *smask, const int *cf, int pmax, // trailing dof: as amg_strength
                       double trunc_factor, DCsr &P, const int *dof = nullptr, int interp_type = 6);
 // aggressive coarsening (hda_amg_agg.hip): second strength graph among the C points of cf (c1: rank of every C point), second PMIS
@@ -472,8 +475,15 @@ void amg_coarsen_second_pass(const DCsr &A, const unsigned char *smask, int num_
 void amg_interp_multipass(const DCsr &A, const unsigned char *smask, const int *cf, DCsr &P);
 void amg_truncate_rows(DCsr &P, int pmax, double trunc_factor); // hypre_BoomerAMGInterpTruncation on finished, column-sorted rows
 // mm-ext+i (interp type 17): the matrix-matrix form of extended+i, W = -D^-1 (I + B) A^s_FC, + InterpTruncation (hda_amg_agg.hip)
+// plus_i = false: mm-ext (type 16), the same products with s_ki := 0
 void amg_interp_mm_extpi(const DCsr &A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, DCsr &P,
-                         const int *dof = nullptr);
+                         const int *dof = nullptr, bool plus_i = true);
+// one-point interpolation (type 100): an F row's single entry of weight 1 towards its strong C neighbour of largest |a_ij| (the first in
+// column order among equals), no entry without a strong C neighbour; C rows identity
+void amg_interp_one_point(const DCsr &A, const unsigned char *smask, const int *cf, DCsr &P);
+// the prolongation types amg_interp_extpi builds, and the refusal of the others by name
+bool        amg_interp_type_built(int t);
+std::string amg_interp_refusal(int t);
 // hypre_ParCSRMatMat-style product C = X*Y, deterministic accumulation order, rows sorted.
 void spgemm(const DCsr &X, const DCsr &Y, DCsr &C);
 // hypre_BoomerAMGBuildCoarseOperator: Ac = R*(A*P) with R = P^T

@@ -339,8 +339,9 @@ __global__ __launch_bounds__(256) void k_mm_q(int n, const int *__restrict__ rp,
    nsc[i] = c; // entries of row i of A^s_FC
 }
 // one walk over row i in column order (FILL = false: counts only): the entries of row i of I + B -- (i, 1) and (k, b_ik) for the
-// strong F neighbours with a non-zero denominator -- and d_i
-template <bool FILL>
+// strong F neighbours with a non-zero denominator -- and d_i.  PLUSI = false (mm-ext, type 16): s_ki := 0, so no neighbour row is
+// searched for a_ki and d_i takes no correction
+template <bool FILL, bool PLUSI>
 __global__ __launch_bounds__(256) void k_mm_rows(int n, const int *__restrict__ rp, const int *__restrict__ cj, const double *__restrict__ v,
                                                  const unsigned char *__restrict__ sm, const int *__restrict__ cf, const int *__restrict__ dof,
                                                  const double *__restrict__ q, int *__restrict__ cnt, const int *__restrict__ brp,
@@ -369,13 +370,14 @@ __global__ __launch_bounds__(256) void k_mm_rows(int n, const int *__restrict__ 
       else if (sm[k] && cf[j] == kF)
       {
          double ski = 0.0;
-         for (int kk = rp[j]; kk < rp[j + 1]; kk++)
-            if (cj[kk] == i && sm[kk]) ski = v[kk];
-         const double den = q[j] + ski;
+         if (PLUSI)
+            for (int kk = rp[j]; kk < rp[j + 1]; kk++)
+               if (cj[kk] == i && sm[kk]) ski = v[kk];
+         const double den = PLUSI ? q[j] + ski : q[j];
          if (den != 0.0)
          {
             const double coef = aij / den;
-            d += coef * ski;
+            if (PLUSI) d += coef * ski;
             if (FILL) { bcj[o] = j; bv[o] = coef; o++; }
             c++;
          }
@@ -418,6 +420,31 @@ __global__ __launch_bounds__(256) void k_mm_p_fill(int n, const int *__restrict_
       pcj[o] = tcj[k];
       pv[o]  = (d != 0.0) ? tv[k] / (-d) : tv[k];
    }
+}
+
+// ---- one-point interpolation (type 100): per F row the strong C neighbour of largest |a_ij|, the first in column order among equals
+// (FILL = false: the row's entry count).  A thread per row like the kernels above: the rows are the operator's own, a handful of entries.
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_one_point(int n, const int *__restrict__ rp, const int *__restrict__ cj, const double *__restrict__ v,
+                                                   const unsigned char *__restrict__ sm, const int *__restrict__ cf, const int *__restrict__ cidx,
+                                                   int *__restrict__ cnt, const int *__restrict__ prp, int *__restrict__ pcj,
+                                                   double *__restrict__ pv)
+{
+   const int i = blockIdx.x * 256 + threadIdx.x;
+   if (i >= n) return;
+   int best = -1;
+   if (cf[i] == kC) best = i;
+   else if (cf[i] == kF)
+   {
+      double mx = -1.0;
+      for (int k = rp[i]; k < rp[i + 1]; k++)
+      {
+         const int j = cj[k];
+         if (sm[k] && cf[j] == kC && fabs(v[k]) > mx) { mx = fabs(v[k]); best = j; }
+      }
+   }
+   if (!FILL) cnt[i] = best >= 0;
+   else if (best >= 0) { pcj[prp[i]] = cidx[best]; pv[prp[i]] = 1.0; }
 }
 
 } // namespace
@@ -531,10 +558,29 @@ void amg_interp_multipass(const DCsr &A, const unsigned char *smask, const int *
    P.reset_plan();
 }
 
+void amg_interp_one_point(const DCsr &A, const unsigned char *smask, const int *cf, DCsr &P)
+{
+   const int n = A.nrows, g = ceil_div(std::max(n, 1), 256);
+   DArray<int> m((size_t)n + 1), cidx((size_t)n + 1), cnt((size_t)n + 1);
+   k_agg_cmark<<<g, 256, 0, STREAM>>>(n, cf, m.data());
+   exclusive_scan(n, m.data(), cidx.data(), nullptr);
+   int nc = 0;
+   HDA_HIP(hipMemcpyAsync(&nc, cidx.data() + n, 4, hipMemcpyDeviceToHost, STREAM));
+   cnt.zero();
+   k_one_point<false><<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), A.val.data(), smask, cf, cidx.data(), cnt.data(), nullptr, nullptr,
+                                            nullptr);
+   finish_rows(n, nc, cnt, P); // (synchronises: nc has arrived)
+   P.ncols = nc;
+   k_one_point<true><<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), A.val.data(), smask, cf, cidx.data(), nullptr, P.rowptr.data(),
+                                           P.col.data(), P.val.data());
+   P.reset_plan();
+}
+
 // hypre's mm-ext+i (interpolation type 17, reference src/internal/amg.c:267-268): W = -D^-1 (I + B) A^s_FC, the product on the
 // deterministic SpGEMM of the Galerkin operator, then InterpTruncation on the finished rows.  Bit-identical to
 // orc_interp_mm_extpi_dof (same order of every sum).
-void amg_interp_mm_extpi(const DCsr &A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, DCsr &P, const int *dof)
+void amg_interp_mm_extpi(const DCsr &A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, DCsr &P, const int *dof,
+                         bool plus_i)
 {
    const int n = A.nrows, g = ceil_div(std::max(n, 1), 256);
    DArray<int> m((size_t)n + 1), cidx((size_t)n + 1), nsc((size_t)n + 1), cb((size_t)n + 1);
@@ -546,14 +592,16 @@ void amg_interp_mm_extpi(const DCsr &A, const unsigned char *smask, const int *c
    nsc.zero();
    cb.zero();
    k_mm_q<<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), A.val.data(), smask, cf, q.data(), nsc.data());
-   k_mm_rows<false><<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), A.val.data(), smask, cf, dof, q.data(), cb.data(), nullptr, nullptr,
-                                          nullptr, nullptr);
+   auto rows_count = plus_i ? k_mm_rows<false, true> : k_mm_rows<false, false>;
+   auto rows_fill  = plus_i ? k_mm_rows<true, true> : k_mm_rows<true, false>;
+   rows_count<<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), A.val.data(), smask, cf, dof, q.data(), cb.data(), nullptr, nullptr, nullptr,
+                                     nullptr);
    Context::get().sync();
    DCsr B, FC, T;
    finish_rows(n, n, cb, B);
    finish_rows(n, nc, nsc, FC);
-   k_mm_rows<true><<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), A.val.data(), smask, cf, dof, q.data(), nullptr, B.rowptr.data(),
-                                         B.col.data(), B.val.data(), dd.data());
+   rows_fill<<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), A.val.data(), smask, cf, dof, q.data(), nullptr, B.rowptr.data(), B.col.data(),
+                                    B.val.data(), dd.data());
    k_mm_fc_fill<<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), A.val.data(), smask, cf, cidx.data(), FC.rowptr.data(), FC.col.data(),
                                       FC.val.data());
    spgemm(B, FC, T); // rows column-sorted, every output entry summed in the order the product enumerates its terms (k ascending)

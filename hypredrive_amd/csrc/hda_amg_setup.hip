@@ -816,6 +816,9 @@ __device__ void qsort_abs(int *L, double *W, int n, int *stack)
    }
 }
 
+// PLUSI = false: classical extended interpolation (type 14) -- the point i itself takes no part in a strong F neighbour's
+// denominator and receives nothing of what that neighbour distributes; everything else is the extended+i arithmetic
+template <bool PLUSI>
 __global__ __launch_bounds__(256) void k_interp_build(
    int n, const int *__restrict__ rp, const int *__restrict__ cj, const double *__restrict__ v,
    const unsigned char *__restrict__ smask, const int *__restrict__ cf,
@@ -977,7 +980,7 @@ __global__ __launch_bounds__(256) void k_interp_build(
          for (int kk = j0; kk < j1; kk++)
          {
             const int m = cj[kk];
-            if (sgn * v[kk] < 0.0 && (m == i || find(m) >= 0)) sum += v[kk];
+            if (sgn * v[kk] < 0.0 && ((PLUSI && m == i) || find(m) >= 0)) sum += v[kk];
          }
          if (sum != 0.0)
          {
@@ -989,7 +992,7 @@ __global__ __launch_bounds__(256) void k_interp_build(
                {
                   const int em = find(m);
                   if (em >= 0) W[em] += distribute * v[kk];
-                  else if (m == i) diagonal += distribute * v[kk];
+                  else if (PLUSI && m == i) diagonal += distribute * v[kk];
                }
             }
          }
@@ -1122,7 +1125,8 @@ __device__ __forceinline__ double group_lane_value(double v, int l)
    else return __shfl(v, l, G);
 }
 
-template <int G>
+// PLUSI = false: classical extended interpolation (type 14), as in k_interp_build
+template <int G, bool PLUSI>
 __global__ __launch_bounds__(256, 5) void k_interp_wave(
    int n, const int *__restrict__ rp, const int *__restrict__ cj, const double *__restrict__ v,
    const unsigned char *__restrict__ smask, const unsigned char *__restrict__ sc, const int *__restrict__ cf, const int *__restrict__ nsC,
@@ -1484,7 +1488,7 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
          for (int f = lane; f < nbr_total; f += G)
          {
             const int m = ncol[f] & 0x7FFFFFFF;
-            ncol[f]     = (m == i) ? -2 : lookup(m);
+            ncol[f]     = (PLUSI && m == i) ? -2 : lookup(m);
          }
          WAVE_SYNC();
          // 4c. one lane per strong-F neighbour: the ordered sum over the qualifying entries of its row
@@ -1603,7 +1607,7 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
                   bool cond = false;
                   if (mm[u] >= 0 && sgn * aa[u] < 0.0)
                   {
-                     pp[u] = (mm[u] == i) ? -2 : lookup(mm[u]);
+                     pp[u] = (PLUSI && mm[u] == i) ? -2 : lookup(mm[u]);
                      cond  = pp[u] != -1;
                   }
                   unsigned long long bits = gballot(cond);
@@ -1659,7 +1663,7 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
                {
                   const int m = nb_col(k, kk);
                   a           = nb_val(k, kk);
-                  if (sgn * a < 0.0) cond = (m == i) || lookup(m) >= 0;
+                  if (sgn * a < 0.0) cond = (PLUSI && m == i) || lookup(m) >= 0;
                }
                unsigned long long bits = gballot(cond);
                while (bits)
@@ -1683,7 +1687,7 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
                      {
                         const int pos = lookup(m);
                         if (pos >= 0) Wv[pos] += distribute * a;
-                        else if (m == i) misc[0] += distribute * a;
+                        else if (PLUSI && m == i) misc[0] += distribute * a;
                      }
                   }
                   WAVE_SYNC();
@@ -1840,16 +1844,44 @@ __global__ __launch_bounds__(256) void k_interp_gather(int n, const long long *_
    }
 }
 
+bool amg_interp_type_built(int t) { return t == 3 || t == 4 || t == 6 || t == 8 || t == 14 || t == 16 || t == 17 || t == 100; }
+
+std::string amg_interp_refusal(int t)
+{ // names: the prolongation_type keys of the YAML reader (hda_yaml.cpp, kInterp)
+   static const struct { int t; const char *name; } names[] = {
+      {0, "mod_classical"}, {1, "least_squares"}, {2, "mod_classical_he"}, {5, "multipass_sep_weights"}, {7, "extended+i_c"},
+      {9, "standard_sep_weights"}, {10, "blk_classical"}, {11, "blk_classical_diag"}, {12, "f_f"}, {13, "f_f1"}, {18, "mm_extended+e"},
+      {24, "blk_direct"}};
+   std::string what = "interpolation type " + std::to_string(t);
+   for (const auto &e : names)
+      if (e.t == t) what = std::string("interpolation type ") + e.name + " (" + std::to_string(t) + ")";
+   return what + " is not implemented on MI355X: direct_sep_weights (3), multipass (4), extended+i (6), standard (8), extended (14), "
+                 "mm_extended (16), mm_extended+i (17) and one_point (100) are";
+}
+
 void amg_interp_extpi(const DCsr &A, const unsigned char *smask, const int *cf, int pmax,
                       double trunc_factor, DCsr &P, const int *dof, int interp_type)
 {
-   HDA_REQUIRE(interp_type == 6 || interp_type == 17 || interp_type == 3 || interp_type == 8, "interpolation type not implemented");
-   if (interp_type == 17)
-   { // mm-ext+i is an operator of its own, built from sparse products (hda_amg_agg.hip)
-      amg_interp_mm_extpi(A, smask, cf, pmax, trunc_factor, P, dof);
+   HDA_REQUIRE(amg_interp_type_built(interp_type), amg_interp_refusal(interp_type).c_str());
+   if (interp_type == 17 || interp_type == 16)
+   { // mm-ext+i and mm-ext are operators of their own, built from sparse products (hda_amg_agg.hip)
+      amg_interp_mm_extpi(A, smask, cf, pmax, trunc_factor, P, dof, interp_type == 17);
       return;
    }
-   const int itype = (interp_type == 3 || interp_type == 8) ? interp_type : 6;
+   if (interp_type == 100)
+   { // one-point interpolation has nothing to truncate
+      amg_interp_one_point(A, smask, cf, P);
+      return;
+   }
+   if (interp_type == 4)
+   { // multipass on the level's one-pass splitting, then the truncation of the interpolation block
+      HDA_REQUIRE(!dof, "multipass interpolation (4) is implemented on a scalar problem only");
+      amg_interp_multipass(A, smask, cf, P);
+      amg_truncate_rows(P, pmax, trunc_factor);
+      return;
+   }
+   const bool plus_i = interp_type != 14; // 14: extended, the extended+i arithmetic without the point i itself
+   const int  itype  = (interp_type == 3 || interp_type == 8) ? interp_type : 6;
    const int n = A.nrows;
    const int g = ceil_div(std::max(n, 1), 256);
    DArray<int>       nsC((size_t)n + 1), ub((size_t)n + 1), hsz((size_t)n + 1), cmark((size_t)n + 1), cidx((size_t)n + 1), nt((size_t)n + 1);
@@ -1910,6 +1942,11 @@ void amg_interp_extpi(const DCsr &A, const unsigned char *smask, const int *cf, 
    DArray<int> pcnt((size_t)n + 1);
    pcnt.zero();
    HDA_TRACE("  interp: build (tot_u=%lld tot_h=%lld nc=%d maxrow=%d maxub=%d maxnbr=%d lanes/row=%d caps %d %d %d)", tot_u, tot_h, nc, hmx[0], hmx[1], hmx[2], use_wave ? G : 1, cap_row, cap_ub, cap_nbr);
+   auto build_rows = [&](const unsigned char *mode) { // the thread-per-row kernel: on the rows flagged in mode, or on all of them
+      auto kern = plus_i ? k_interp_build<true> : k_interp_build<false>;
+      kern<<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), A.val.data(), smask, cf, uofs.data(), hofs.data(), lcol.data(), lw.data(),
+                                  htab.data(), pmax, trunc_factor, pcnt.data(), mode, dof, itype);
+   };
    if (use_wave)
    {
       const size_t lds = interp_wave_doubles(cap_row, cap_ub, cap_nbr) * 8 * gpb;
@@ -1946,10 +1983,20 @@ void amg_interp_extpi(const DCsr &A, const unsigned char *smask, const int *cf, 
                                                                       lcol.data(), lw.data(), pcnt.data(), dof, s3_scan, prof.data(), reg_nbr,
                                                                       scc.data() ? scofs.data() : nullptr, scc.data());
       };
-      if (G == 8) launch(k_interp_wave<8>);
-      else if (G == 16) launch(k_interp_wave<16>);
-      else if (G == 32) launch(k_interp_wave<32>);
-      else launch(k_interp_wave<64>);
+      if (plus_i)
+      {
+         if (G == 8) launch(k_interp_wave<8, true>);
+         else if (G == 16) launch(k_interp_wave<16, true>);
+         else if (G == 32) launch(k_interp_wave<32, true>);
+         else launch(k_interp_wave<64, true>);
+      }
+      else
+      {
+         if (G == 8) launch(k_interp_wave<8, false>);
+         else if (G == 16) launch(k_interp_wave<16, false>);
+         else if (G == 32) launch(k_interp_wave<32, false>);
+         else launch(k_interp_wave<64, false>);
+      }
       if (want_prof)
       {
          unsigned long long h[10];
@@ -1961,12 +2008,9 @@ void amg_interp_extpi(const DCsr &A, const unsigned char *smask, const int *cf, 
       }
       // the rows the wave kernel left to the thread kernel (rowmode): also when none of them needs a hash table
       // (C points and non-interpolated F points among them still have to report their entry count)
-      k_interp_build<<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), A.val.data(), smask, cf, uofs.data(), hofs.data(),
-                                            lcol.data(), lw.data(), htab.data(), pmax, trunc_factor, pcnt.data(), rowmode.data(), dof, itype);
+      build_rows(rowmode.data());
    }
-   else
-      k_interp_build<<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), A.val.data(), smask, cf, uofs.data(), hofs.data(),
-                                            lcol.data(), lw.data(), htab.data(), pmax, trunc_factor, pcnt.data(), nullptr, dof, itype);
+   else build_rows(nullptr);
    HDA_TRACE("  interp: build done");
    P.nrows = n;
    P.ncols = nc;
@@ -2700,8 +2744,8 @@ void Amg::build_hierarchy(const DCsr &A)
    HDA_REQUIRE(prm.coarsen_type == 8 || prm.coarsen_type == 10, "device AMG setup implements PMIS (8) and, on one rank, HMIS (10) coarsening");
    // 17 = "mm-ext+i" (reference src/internal/amg.c:266-268): hypre's matrix-matrix formulation of extended+i -- an operator of its
    // own (denominators over the strong C neighbours of the intermediate point, no sign filter), built from sparse products
-   HDA_REQUIRE(prm.interp_type == 6 || prm.interp_type == 17 || prm.interp_type == 3 || prm.interp_type == 8,
-               "interpolation type is not implemented on MI355X: extended+i (6), its matrix-matrix form mm-ext+i (17), direct_sep_weights (3) and standard (8) are");
+   HDA_REQUIRE(amg_interp_type_built(prm.interp_type), amg_interp_refusal(prm.interp_type).c_str());
+   HDA_REQUIRE(prm.interp_type != 4 || prm.num_functions <= 1, "multipass interpolation (prolongation_type 4) is implemented on a scalar problem only");
    auto known = [](int t) { return is_jacobi_type(t) || is_gs_type(t) || is_two_stage_type(t) || t == 16; };
    HDA_REQUIRE(known(prm.relax_down) && known(prm.relax_up),
                "device V-cycle implements Jacobi (0, 7, 18), hybrid Gauss-Seidel (3, 4, 6, 8, 13, 14), two-stage Gauss-Seidel (11, 12) and "

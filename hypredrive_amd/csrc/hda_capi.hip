@@ -507,6 +507,34 @@ extern "C" int hda_interp_mm_extpi(hda_csr_t A, const unsigned char *smask, cons
    HDA_CATCH
 }
 
+// extended (14), mm-ext (16) and one-point (100) interpolation for a given strength mask and splitting
+static int interp_of_type(int interp_type, hda_csr_t A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, hda_csr_t *P)
+{
+   HDA_TRY
+   const DCsr           &m = A->get();
+   DArray<unsigned char> sm;
+   DArray<int>           dcf;
+   sm.upload(smask, (size_t)std::max(m.nnz, 1));
+   dcf.upload(cf, (size_t)std::max(m.nrows, 1));
+   auto h = std::make_unique<hda_csr_s>();
+   amg_interp_extpi(m, sm.data(), dcf.data(), pmax, trunc_factor, h->m, nullptr, interp_type);
+   Context::get().sync();
+   *P = h.release();
+   HDA_CATCH
+}
+extern "C" int hda_interp_extended(hda_csr_t A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, hda_csr_t *P)
+{
+   return interp_of_type(14, A, smask, cf, pmax, trunc_factor, P);
+}
+extern "C" int hda_interp_mm_ext(hda_csr_t A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, hda_csr_t *P)
+{
+   return interp_of_type(16, A, smask, cf, pmax, trunc_factor, P);
+}
+extern "C" int hda_interp_one_point(hda_csr_t A, const unsigned char *smask, const int *cf, hda_csr_t *P)
+{
+   return interp_of_type(100, A, smask, cf, 0, 0.0, P);
+}
+
 // aggressive coarsening pieces (hda_amg_agg.hip), one entry per stage for the per-kernel parity tests
 extern "C" int hda_second_strength(hda_csr_t A, const unsigned char *smask, const int *cf, int num_paths, hda_csr_t *S2)
 {

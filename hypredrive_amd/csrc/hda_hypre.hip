@@ -1336,7 +1336,7 @@ extern "C" HYPRE_Int HYPRE_BoomerAMGSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, 
       //  sweeps need every level's splitting: both are built on the gathered operator)
       // (aggressive levels: their second strength graph reaches two ghost layers deep -- built on the gathered operator too)
       // (mm-ext+i, type 17: its sparse products are formed on the gathered operator as well; direct (3) and standard (8) interpolation:
-      //  options beside the path, one-rank kernels)
+      //  options beside the path, one-rank kernels; so are extended (14), mm-ext (16), one-point (100) and multipass (4))
       if ((mode && !strcmp(mode, "replicated")) || s->ap.coarsen_type != 8 || s->ap.num_functions > 1 || s->ap.smooth_num_levels > 1 || s->ap.agg_num_levels > 0 ||
           s->ap.interp_type != 6 || s->ap.restrict_type != 0 || !s->ap.points_down.empty() || !s->ap.points_up.empty())
          s->amg->setup_dist(A->A, A->halo, A->part, A->ghost_gids);

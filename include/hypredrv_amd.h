@@ -131,6 +131,14 @@ int hda_interp_direct(hda_csr_t A, const unsigned char *smask, const int *cf, in
 /* hypre's mm-ext+i (interpolation type 17, "mm-ext+i" in reference src/internal/amg.c:267-268; the interpolation of
  * examples/refOutput/ex8.txt:26-78): the matrix-matrix form of extended+i, W = -D^-1 (I + B) A^s_FC, + InterpTruncation */
 int hda_interp_mm_extpi(hda_csr_t A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, hda_csr_t *P);
+/* The plain members of the two long-range families, each + InterpTruncation:
+ * extended (interpolation type 14): extended+i without the point i itself in a strong F neighbour's denominator or in the diagonal;
+ * mm-ext (type 16, "mm_extended"): mm-ext+i with s_ki := 0, W = -D^-1 (I + B) A^s_FC with b_ik = a_ik / q_k */
+int hda_interp_extended(hda_csr_t A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, hda_csr_t *P);
+int hda_interp_mm_ext(hda_csr_t A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, hda_csr_t *P);
+/* one-point interpolation (type 100, the partner of AIR restriction): an F row's one entry of weight 1 towards its strong C neighbour
+ * of largest |a_ij| (the first in column order among equals); no entry without a strong C neighbour; no truncation */
+int hda_interp_one_point(hda_csr_t A, const unsigned char *smask, const int *cf, hda_csr_t *P);
 /* hypre_BoomerAMGBuildStdInterp without separation of weights (interpolation type 8, "standard" in reference
  * src/internal/amg.c:258; the configuration examples/refOutput/ex8.txt:74 echoes for its fifth variant) + InterpTruncation */
 int hda_interp_standard(hda_csr_t A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, hda_csr_t *P);
