@@ -91,6 +91,7 @@ SYMBOLS = [
     "hda_second_strength", "hda_coarsen_second_pass", "hda_interp_multipass", "hda_truncate_rows",
     "hda_interp_mm_extpi", "hda_interp_extended", "hda_interp_mm_ext", "hda_interp_one_point", "hda_interp_standard", "hda_set_overlap", "hda_marker", "hda_relax_blocks", "hda_l1_norms_blocks", "hda_hmis_blocks", "hda_amg_blocks", "hda_amg_level_blocks",
     "hda_csr_form", "hda_spmv_mode", "hda_air_restriction",
+    "hda_cljp", "hda_rs_blocks", "hda_falgout_blocks", "hda_measure_rnd",
 ]
 
 
@@ -152,6 +153,10 @@ def load():
     L.hda_relax_blocks.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, P(C.c_int64), dp, dp]
     L.hda_l1_norms_blocks.argtypes = [vp, C.c_int, C.c_int, P(C.c_int64), dp]
     L.hda_hmis_blocks.argtypes = [vp, P(C.c_ubyte), C.c_int, P(C.c_int64), C.c_uint64, C.c_int, ip]
+    L.hda_cljp.argtypes = [vp, P(C.c_ubyte), C.c_uint64, C.c_int, C.c_int64, ip, ip]
+    L.hda_rs_blocks.argtypes = [vp, P(C.c_ubyte), C.c_int, P(C.c_int64), ip]
+    L.hda_falgout_blocks.argtypes = [vp, P(C.c_ubyte), C.c_int, P(C.c_int64), C.c_uint64, C.c_int, ip, ip]
+    L.hda_measure_rnd.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_int64, dp]
     L.hda_amg_blocks.argtypes = [vp]
     L.hda_marker.argtypes = [C.c_int]
     L.hda_amg_level_blocks.argtypes = [vp, C.c_int, P(C.c_int64)]
@@ -327,6 +332,32 @@ class Csr:
         pt = np.ascontiguousarray(part, dtype=np.int64)
         _check(load().hda_hmis_blocks(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), len(pt) - 1, pt.ctypes.data_as(C.POINTER(C.c_int64)),
                                       seed, level, _ip(cf)))
+        return cf[:self.nrows]
+
+    # coarsen types 0 / 1 / 6; last_rounds: the CLJP rounds of the latest cljp / falgout_blocks call
+    def cljp(self, smask, seed=2747, level=0, row_offset=0):
+        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
+        cf = np.zeros(max(self.nrows, 1), dtype=np.int32)
+        rounds = C.c_int(0)
+        _check(load().hda_cljp(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), seed, level, row_offset, _ip(cf), C.byref(rounds)))
+        self.last_rounds = rounds.value
+        return cf[:self.nrows]
+
+    def rs_blocks(self, smask, part=None):
+        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
+        cf = np.zeros(max(self.nrows, 1), dtype=np.int32)
+        pt = np.ascontiguousarray([0, self.nrows] if part is None else part, dtype=np.int64)
+        _check(load().hda_rs_blocks(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), len(pt) - 1, pt.ctypes.data_as(C.POINTER(C.c_int64)), _ip(cf)))
+        return cf[:self.nrows]
+
+    def falgout_blocks(self, smask, part=None, seed=2747, level=0):
+        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
+        cf = np.zeros(max(self.nrows, 1), dtype=np.int32)
+        pt = np.ascontiguousarray([0, self.nrows] if part is None else part, dtype=np.int64)
+        rounds = C.c_int(0)
+        _check(load().hda_falgout_blocks(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), len(pt) - 1, pt.ctypes.data_as(C.POINTER(C.c_int64)),
+                                         seed, level, _ip(cf), C.byref(rounds)))
+        self.last_rounds = rounds.value
         return cf[:self.nrows]
 
     def strength(self, theta=0.25, max_row_sum=0.9):
@@ -898,6 +929,13 @@ def memory_driver_stats(reset=False):
 def memory_trim():
     """cached device blocks of this thread's allocator back to the driver (another process is about to need the memory)"""
     _check(load().hda_memory_trim())
+
+
+def measure_rnd(n, seed=2747, level=0, row_offset=0):
+    """The random part in [0, 1) of the coarsening measures of n rows (the stream of PMIS, HMIS, CLJP and Falgout)."""
+    out = np.zeros(max(n, 1))
+    _check(load().hda_measure_rnd(n, seed, level, row_offset, _dp(out)))
+    return out[:n]
 
 
 def sync():

@@ -27,7 +27,7 @@ struct IluParams {
 
 struct AmgParams {
    // coarsening (src/internal/amg.c:138-157)
-   int    coarsen_type    = 8;  // PMIS (hypre-GPU default); 10 HMIS = Ruge first pass (one device thread, small systems); others not on device
+   int    coarsen_type    = 8;  // PMIS (hypre-GPU default); 10 HMIS = Ruge first pass (one device thread, small systems); 0 CLJP, 1 RS, 6 Falgout; others not on device
    double strong_th       = 0.25;
    double max_row_sum     = 0.9;
    int    max_coarse_size = 64;
@@ -463,6 +463,17 @@ void amg_pmis(const DCsr &A, const unsigned char *smask, uint64_t seed, int leve
 // hypre_BoomerAMGCoarsenHMIS (coarsen type 10) on the row blocks part (V + 1 row starts; empty = one block): Ruge first pass per
 // block, interior C points kept, PMIS from there
 void amg_hmis(const DCsr &A, const unsigned char *smask, const std::vector<int> &part, uint64_t seed, int level, int *cf);
+// CLJP (coarsen type 0), Ruge-Stueben first + second pass per row block (1) and Falgout (6: RS per block, interior C points kept, CLJP
+// from there) as tests/coarsen_reference.py defines them.  amg_cljp / amg_falgout return the number of CLJP rounds.
+// amg_measure_rnd: the random part of the measures, rnd[i] (device) for global row row_offset + i -- the stream PMIS uses.
+int  amg_cljp(const DCsr &A, const unsigned char *smask, uint64_t seed, int level, long long row_offset, int *cf);
+void amg_rs(const DCsr &A, const unsigned char *smask, const std::vector<int> &part, int *cf);
+int  amg_falgout(const DCsr &A, const unsigned char *smask, const std::vector<int> &part, uint64_t seed, int level, int *cf);
+void amg_measure_rnd(int n, uint64_t seed, int level, long long row_offset, double *rnd);
+// the coarsening types the setup builds, their YAML names (nullptr: no name), and the refusal of the others by name
+bool        amg_coarsen_type_built(int t);
+const char *amg_coarsen_name(int t);
+std::string amg_coarsen_refusal(int t);
 // hypre_BoomerAMGBuildExtPIInterp (interp_type 6 / 17) or hypre_BoomerAMGBuildDirInterp with separation of weights (3),
 // then InterpTruncation: P (nrows x nc), rows column-sorted.  Also standard (8), extended (14), mm-ext (16), one-point (100) and
 // multipass on the given one-pass splitting (4).

@@ -398,6 +398,58 @@ extern "C" int hda_hmis_blocks(hda_csr_t A, const unsigned char *smask, int nblk
    HDA_CATCH
 }
 
+// CLJP / RS / Falgout coarsening; rounds (may be NULL): the CLJP rounds taken
+extern "C" int hda_cljp(hda_csr_t A, const unsigned char *smask, uint64_t seed, int level, int64_t row_offset, int *cf, int *rounds)
+{
+   HDA_TRY
+   const DCsr           &m = A->get();
+   DArray<unsigned char> sm((size_t)std::max(m.nnz, 1));
+   if (m.nnz) sm.upload(smask, (size_t)m.nnz);
+   DArray<int> dcf((size_t)std::max(m.nrows, 1));
+   const int   r = amg_cljp(m, sm.data(), seed, level, row_offset, dcf.data());
+   if (rounds) *rounds = r;
+   if (m.nrows) dcf.download(cf, (size_t)m.nrows);
+   HDA_CATCH
+}
+
+extern "C" int hda_rs_blocks(hda_csr_t A, const unsigned char *smask, int nblk, const int64_t *part, int *cf)
+{
+   HDA_TRY
+   const DCsr            &m  = A->get();
+   const std::vector<int> hp = to_part(nblk, part, m.nrows);
+   DArray<unsigned char>  sm((size_t)std::max(m.nnz, 1));
+   if (m.nnz) sm.upload(smask, (size_t)m.nnz);
+   DArray<int> dcf((size_t)std::max(m.nrows, 1));
+   amg_rs(m, sm.data(), hp, dcf.data());
+   if (m.nrows) dcf.download(cf, (size_t)m.nrows);
+   HDA_CATCH
+}
+
+extern "C" int hda_falgout_blocks(hda_csr_t A, const unsigned char *smask, int nblk, const int64_t *part, uint64_t seed, int level, int *cf,
+                                  int *rounds)
+{
+   HDA_TRY
+   const DCsr            &m  = A->get();
+   const std::vector<int> hp = to_part(nblk, part, m.nrows);
+   DArray<unsigned char>  sm((size_t)std::max(m.nnz, 1));
+   if (m.nnz) sm.upload(smask, (size_t)m.nnz);
+   DArray<int> dcf((size_t)std::max(m.nrows, 1));
+   const int   r = amg_falgout(m, sm.data(), hp, seed, level, dcf.data());
+   if (rounds) *rounds = r;
+   if (m.nrows) dcf.download(cf, (size_t)m.nrows);
+   HDA_CATCH
+}
+
+extern "C" int hda_measure_rnd(int n, uint64_t seed, int level, int64_t row_offset, double *rnd)
+{
+   HDA_TRY
+   HDA_REQUIRE(n >= 0, "hda_measure_rnd: negative length");
+   DArray<double> d((size_t)std::max(n, 1));
+   amg_measure_rnd(n, seed, level, row_offset, d.data());
+   if (n) d.download(rnd, (size_t)n);
+   HDA_CATCH
+}
+
 extern "C" int hda_dot(int n, const double *x, const double *y, double *result)
 {
    HDA_TRY

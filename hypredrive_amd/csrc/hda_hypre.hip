@@ -1348,7 +1348,9 @@ extern "C" HYPRE_Int HYPRE_BoomerAMGSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, 
    {
       printf("\n BoomerAMG (MI355X): %d levels, grid complexity %.6f, operator complexity %.6f\n", s->amg->num_levels(),
              s->amg->grid_complexity(), s->amg->operator_complexity());
-      if (s->amg->blocks_used > 1) printf(" %d row blocks (hybrid Gauss-Seidel / HMIS as on %d ranks)\n", s->amg->blocks_used, s->amg->blocks_used);
+      printf(" coarsening %s (%d)\n", amg_coarsen_name(s->ap.coarsen_type) ? amg_coarsen_name(s->ap.coarsen_type) : "?", s->ap.coarsen_type);
+      if (s->amg->blocks_used > 1)
+         printf(" %d row blocks (hybrid Gauss-Seidel / HMIS / RS / Falgout as on %d ranks)\n", s->amg->blocks_used, s->amg->blocks_used);
       printf("\n");
    }
    HY_CATCH

@@ -114,6 +114,14 @@ int hda_l1_norms(hda_csr_t A, int option, double *l1);
 int hda_relax_blocks(hda_csr_t A, int relax_type, double weight, int sweeps, int nblk, const int64_t *part, const double *b, double *x);
 int hda_l1_norms_blocks(hda_csr_t A, int option, int nblk, const int64_t *part, double *l1);
 int hda_hmis_blocks(hda_csr_t A, const unsigned char *smask, int nblk, const int64_t *part, uint64_t seed, int level, int *cf);
+/* coarsen types 0, 1 and 6 as DESIGN section 14 defines them: CLJP on the whole matrix (row_offset: global id of row 0 in the measure
+ * stream); Ruge-Stueben first and second pass inside every row block; Falgout = that, interior C points kept, CLJP from there.
+ * rounds (may be NULL): CLJP rounds taken.  hda_measure_rnd: the random part in [0, 1) of the measures of n rows, the stream PMIS,
+ * HMIS, CLJP and Falgout share. */
+int hda_cljp(hda_csr_t A, const unsigned char *smask, uint64_t seed, int level, int64_t row_offset, int *cf, int *rounds);
+int hda_rs_blocks(hda_csr_t A, const unsigned char *smask, int nblk, const int64_t *part, int *cf);
+int hda_falgout_blocks(hda_csr_t A, const unsigned char *smask, int nblk, const int64_t *part, uint64_t seed, int level, int *cf, int *rounds);
+int hda_measure_rnd(int n, uint64_t seed, int level, int64_t row_offset, double *rnd);
 
 /* ---- K4 / K5 / K6 ------------------------------------------------------------------ */
 /* hypre_BoomerAMGCreateS */
