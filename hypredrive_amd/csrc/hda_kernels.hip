@@ -1482,15 +1482,23 @@ static void ensure_window(const DCsr &A)
    HDA_TRACE("windowed CSR for %d x %d, nnz %d: %.3f distinct columns per entry, at most %d in a chunk", A.nrows, A.ncols, A.nnz, ratio, m);
 }
 
-template <int MODE, bool DOT, bool VC, bool SPLIT, bool RUNS = false>
-__global__ __launch_bounds__(256) void k_spmv_win(int nw, const int *__restrict__ wmeta, const int *__restrict__ rowptr,
+// EPI (last, so that the names of the plain instantiations keep their prefix): the scaled second result is a compile-time property --
+// only the launches armed by spmv_with_scaled_copy run an instantiation that holds any dinv2 / out2 code.
+// amdgpu_num_sgpr(80): the grid (kRedBlocks = 8 workgroups on each of 256 CUs, every workgroup walking its share of the chunks) counts
+// on all of it being resident at once.  With dinv2 / out2 as run-time arguments the value-coded instantiation went from 77 to 83 scalar
+// registers, i.e. from an allocation of 80 to one of 96 per wave, and from 0.215 to 0.349 ms per level-0 transfer product at 256^3 with
+// the same instructions, vector registers, LDS and traffic (profiles/transfer_kernels.md: the allocation is the one column of the kernel
+// trace that differs between the fast and the slow arms).  No instantiation may cross that line again unnoticed.
+template <int MODE, bool DOT, bool VC, bool SPLIT, bool RUNS = false, bool EPI = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_spmv_win(int nw, const int *__restrict__ wmeta, const int *__restrict__ rowptr,
                                                   const unsigned short *__restrict__ lidx, const int *__restrict__ ucol,
                                                   const double *__restrict__ val, const double *__restrict__ x, double alpha, double beta,
                                                   const double *yin, const double *__restrict__ b, const double *__restrict__ dinv,
                                                   const double *__restrict__ w, double *out, double *__restrict__ partial, int nown,
                                                   int prod_len, const unsigned char *__restrict__ code, const double *__restrict__ dval, int pf,
                                                   const double *__restrict__ dinv2 = nullptr, double *__restrict__ out2 = nullptr)
-{ // out2 (MODE_PLAIN only): a second result out2 = dinv2 .* out, as in k_spmv_stream (the next level's zero-guess Jacobi sweep)
+{ // out2 (EPI, MODE_PLAIN only): a second result out2 = dinv2 .* out, as in k_spmv_stream (the next level's zero-guess Jacobi sweep)
+   static_assert(!EPI || (MODE == MODE_PLAIN && !DOT && !SPLIT), "the scaled second result exists for whole plain products only");
    extern __shared__ double smem[];
    double *prod = smem, *xs = smem + prod_len;
    __shared__ double sdict[VC ? 256 : 1];
@@ -1541,7 +1549,7 @@ __global__ __launch_bounds__(256) void k_spmv_win(int nw, const int *__restrict_
          const int r = c.r0 + rr;
          ps          = rowptr[r] - c.k0;
          pe          = rowptr[r + 1] - c.k0;
-         if (MODE == MODE_PLAIN) { if (beta != 0.0) pb = yin[r]; if (DOT) pd = w[r]; }
+         if (MODE == MODE_PLAIN) { if (beta != 0.0) pb = yin[r]; if (DOT) pd = w[r]; if (EPI) pd = dinv2[r]; } // (EPI: never with DOT)
          else if (MODE == MODE_RESID) pb = b[r];
          else { pb = b[r]; pd = dinv[r]; px = x[r]; }
       }
@@ -1648,7 +1656,7 @@ __global__ __launch_bounds__(256) void k_spmv_win(int nw, const int *__restrict_
             {
                o0 = (beta == 0.0) ? alpha * sum : alpha * sum + beta * (first ? cb : yin[r]);
                if (DOT) acc += o0 * (first ? cd : w[r]);
-               if (out2) out2[r] = dinv2[r] * o0;
+               if (EPI) out2[r] = (first ? cd : dinv2[r]) * o0; // the scale travels with the row's other operands, one chunk ahead
             }
             else if (MODE == MODE_RESID) o0 = (first ? cb : b[r]) - sum;
             else
@@ -2038,33 +2046,41 @@ static bool launch_spmv_impl(const DCsr &A, const double *x, double alpha, doubl
          const int    plen = kWChunk + A.maxrow;
          const size_t wlds = sizeof(double) * (size_t)(plen + A.win_maxu);
          const int    wg   = DOT ? gmax : std::min(gmax, ((A.nwin + 7) / 8) * 8);
-         // a scaled second result asked for by spmv_with_scaled_copy (whole products only, not the owned-column half)
+         // a scaled second result asked for by spmv_with_scaled_copy (whole products only, not the owned-column half): its own
+         // instantiation (EPI) -- a launch that is not armed runs a kernel without any dinv2 / out2 code
+         bool          wepi   = false;
          const double *wepi_d = nullptr;
          double       *wepi_o = nullptr;
          if (MODE == MODE_PLAIN && !DOT && !split && g_epilogue.out2)
          {
+            wepi   = true;
             wepi_d = g_epilogue.dinv2;
             wepi_o = g_epilogue.out2;
             g_epilogue.done = true;
          }
-#define HDA_WIN(VCF, SPF, CODE, DICT)                                                                                                   \
-   k_spmv_win<MODE, DOT, VCF, SPF><<<wg, 256, wlds, STREAM>>>(A.nwin, A.wmeta.data(), A.rowptr.data(), A.lidx.data(), A.ucol.data(),     \
-                                                              A.val.data(), x, alpha, beta, yin, b, dinv, w, out, partial, nown, plen,  \
-                                                              CODE, DICT, win_pf(), wepi_d, wepi_o)
+#define HDA_WIN(VCF, SPF, RUNF, EPIF, CODE, DICT)                                                                                                \
+   k_spmv_win<MODE, DOT, VCF, SPF, RUNF, EPIF><<<wg, 256, wlds, STREAM>>>(A.nwin, A.wmeta.data(), A.rowptr.data(), A.lidx.data(), A.ucol.data(),  \
+                                                                          A.val.data(), x, alpha, beta, yin, b, dinv, w, out, partial, nown,     \
+                                                                          plen, CODE, DICT, win_pf(), wepi_d, wepi_o)
+         // (EPI exists for whole plain products without a dot alone: the constant keeps every other MODE / DOT from instantiating it)
+         constexpr bool kEpi = MODE == MODE_PLAIN && !DOT;
          if (form == SpmvForm::WindowRuns)
          { // run form (never value-coded)
-            if (split) k_spmv_win<MODE, DOT, false, true, true><<<wg, 256, wlds, STREAM>>>(A.nwin, A.wmeta.data(), A.rowptr.data(), A.lidx.data(), A.ucol.data(), A.val.data(), x, alpha, beta, yin, b, dinv, w, out, partial, nown, plen, nullptr, nullptr, win_pf());
-            else k_spmv_win<MODE, DOT, false, false, true><<<wg, 256, wlds, STREAM>>>(A.nwin, A.wmeta.data(), A.rowptr.data(), A.lidx.data(), A.ucol.data(), A.val.data(), x, alpha, beta, yin, b, dinv, w, out, partial, nown, plen, nullptr, nullptr, win_pf(), wepi_d, wepi_o);
+            if (split) { HDA_WIN(false, true, true, false, nullptr, nullptr); }
+            else if (wepi) { HDA_WIN(false, false, true, kEpi, nullptr, nullptr); }
+            else { HDA_WIN(false, false, true, false, nullptr, nullptr); }
          }
          else if (A.coded == 2)
          {
-            if (split) { HDA_WIN(true, true, A.code.data(), A.dict_val.data()); }
-            else { HDA_WIN(true, false, A.code.data(), A.dict_val.data()); }
+            if (split) { HDA_WIN(true, true, false, false, A.code.data(), A.dict_val.data()); }
+            else if (wepi) { HDA_WIN(true, false, false, kEpi, A.code.data(), A.dict_val.data()); }
+            else { HDA_WIN(true, false, false, false, A.code.data(), A.dict_val.data()); }
          }
          else
          {
-            if (split) { HDA_WIN(false, true, nullptr, nullptr); }
-            else { HDA_WIN(false, false, nullptr, nullptr); }
+            if (split) { HDA_WIN(false, true, false, false, nullptr, nullptr); }
+            else if (wepi) { HDA_WIN(false, false, false, kEpi, nullptr, nullptr); }
+            else { HDA_WIN(false, false, false, false, nullptr, nullptr); }
          }
 #undef HDA_WIN
          return true;
