@@ -92,6 +92,7 @@ SYMBOLS = [
     "hda_interp_mm_extpi", "hda_interp_extended", "hda_interp_mm_ext", "hda_interp_one_point", "hda_interp_standard", "hda_set_overlap", "hda_marker", "hda_relax_blocks", "hda_l1_norms_blocks", "hda_hmis_blocks", "hda_amg_blocks", "hda_amg_level_blocks",
     "hda_csr_form", "hda_spmv_mode", "hda_air_restriction",
     "hda_cljp", "hda_rs_blocks", "hda_falgout_blocks", "hda_measure_rnd",
+    "hda_schwarz_create", "hda_schwarz_domains", "hda_schwarz_info", "hda_precond_time",
 ]
 
 
@@ -185,6 +186,10 @@ def load():
     L.hda_ilu_factors.argtypes = [vp, C.c_int, P(vp)]
     L.hda_ilu_create_blocks.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int64), P(vp)]
     L.hda_ilu_blocks.argtypes = [vp, C.c_int]
+    L.hda_schwarz_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int64), C.c_int, C.c_double, P(vp)]
+    L.hda_schwarz_domains.argtypes = [vp, P(C.c_int), ip, ip]
+    L.hda_schwarz_info.argtypes = [vp, P(C.c_int64), P(C.c_double)]
+    L.hda_precond_time.argtypes = [vp, C.c_int, P(C.c_double)]
     L.hda_set_overlap.argtypes = [C.c_int]
     L.hda_set_overlap.restype = None
     L.hda_amg_num_levels.argtypes = [vp]
@@ -684,6 +689,65 @@ class Ilu:
         z = np.zeros_like(r)
         _check(load().hda_amg_vcycle(self.h, _dp(r), _dp(z)))
         return z
+
+
+SCHWARZ_VARIANTS = {"ras": 0, "ras-iluk": 0, "as": 1, "as-iluk": 1}
+
+
+class Schwarz:
+    """'preconditioner: schwarz': restricted (ras) or additive (as) Schwarz on V row blocks grown by `overlap` layers of A's stored
+    pattern, ILU(fill) subdomain solves; usable as amg= in pcg()/gmres()/fgmres()/bicgstab()."""
+
+    def __init__(self, A, variant="ras", overlap=1, fill=0, blocks=1, block_part=None, max_iter=1, weight=1.0):
+        """blocks: 1 one block, 0 the setup's choice, V the even split unless block_part names the V + 1 row starts"""
+        self.A = A
+        self.h = C.c_void_p()
+        bp = None
+        if block_part is not None:
+            bp = np.ascontiguousarray(block_part, dtype=np.int64)
+            blocks = len(bp) - 1
+        _check(load().hda_schwarz_create(A.h, SCHWARZ_VARIANTS[variant] if isinstance(variant, str) else int(variant), overlap, fill, blocks,
+                                         None if bp is None else bp.ctypes.data_as(C.POINTER(C.c_int64)), max_iter, weight, C.byref(self.h)))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            load().hda_amg_destroy(self.h)
+            self.h = None
+
+    def info(self):
+        """dict: n_ext, nnz_factors, longest_row, global_rows (rows on the global-memory symbolic path), lds_capacity, nnz_A, setup_ms"""
+        v, ms = (C.c_int64 * 6)(), (C.c_double * 4)()
+        _check(load().hda_schwarz_info(self.h, v, ms))
+        return dict(n_ext=v[0], nnz_factors=v[1], longest_row=v[2], global_rows=v[3], lds_capacity=v[4], nnz_A=v[5],
+                    setup_ms=dict(expansion=ms[0], extraction=ms[1], symbolic=ms[2], numeric=ms[3]))
+
+    def domains(self):
+        """(dom_ptr, dom_rows): subdomain b holds the global rows dom_rows[dom_ptr[b]:dom_ptr[b + 1]], ascending"""
+        V = C.c_int()
+        _check(load().hda_schwarz_domains(self.h, C.byref(V), None, None))
+        ptr, rows = np.zeros(V.value + 1, dtype=np.int32), np.zeros(max(self.info()["n_ext"], 1), dtype=np.int32)
+        _check(load().hda_schwarz_domains(self.h, C.byref(V), _ip(ptr), _ip(rows)))
+        return ptr, rows[:ptr[-1]]
+
+    def factors(self):
+        """Block-diagonal factors of all subdomains in the extended numbering (strict lower part L with unit diagonal, rest U)."""
+        out = C.c_void_p()
+        _check(load().hda_ilu_factors(self.h, -1, C.byref(out)))
+        return Csr(out, owned=False, keep=self)
+
+    def apply(self, r):
+        """One application from a zero guess (max_iter iterations x += M^-1 (r - A x))."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        z = np.zeros_like(r)
+        _check(load().hda_amg_vcycle(self.h, _dp(r), _dp(z)))
+        return z
+
+
+def precond_time(M, reps=20):
+    """Average device ms of one application of an Ilu / Schwarz handle (vectors stay on the device)."""
+    ms = C.c_double()
+    _check(load().hda_precond_time(M.h, reps, C.byref(ms)))
+    return ms.value
 
 
 def _krylov(fn, A, b, amg, kp, x0):

@@ -170,8 +170,13 @@ class Ilu {
    const DCsr &factors() const { return LU; }            // strict lower part = L (unit diagonal), rest = U
    double      apply_bytes() const;
    IluParams   prm;
+   // a ready pattern with the values scattered in (ILU(k) of the Schwarz subdomains): numeric factorisation and substitution plans
+   // only; part = row starts of the pattern's diagonal blocks.  Returns the flags of the factorisation (bit 2: zero pivot)
+   int        setup_pattern(DCsr &&pattern, const IluParams &p, const std::vector<int> &part);
+   const int *diag_pos() const { return diag.data(); } // position of every row's diagonal entry in factors()
 
  private:
+   int            factor_and_plan();
    DCsr           LU;
    DCsr           Ls, Us; // tri_solve 0: strict lower triangle / diagonal + upper triangle, one stream each
    DArray<int>    diag;
@@ -189,6 +194,41 @@ class Ilu {
 
 void ilu_solve(Ilu &F, const DCsr &A, const HaloPlan *halo, const double *b, double *x, bool zero_guess, DArray<double> &r,
                DArray<double> &c); // max_iter iterations x += M^-1 (b - A x)
+
+// overlapping Schwarz with ILU(k) subdomain solves (hda_schwarz.hip): V contiguous row blocks grown by `overlap`
+// layers of the stored pattern of A, ILU(fill) of every A[Omega_b, Omega_b], z = w * (restricted | additive) combination of the
+// subdomain solves.  One rank.
+struct SchwarzParams {
+   int                    variant = 0; // 0 ras-iluk (every row takes its owner's value), 1 as-iluk (sum over the subdomains that hold it)
+   int                    overlap = 1, fill = 0, max_iter = 1;
+   double                 weight  = 1.0;
+   int                    blocks  = 1; // as IluParams::blocks
+   std::vector<long long> block_part;
+};
+constexpr int kSchwarzLdsRows = 512; // vertices a row's symbolic search may visit before it leaves the LDS table for the global-memory path
+class Schwarz {
+ public:
+   void        setup(const DCsr &A, const SchwarzParams &p);
+   void        apply(const double *r, double *z); // z = M^-1 r (one pass); r and z must not alias
+   const DCsr &factors() const { return F.factors(); }
+   int         num_domains() const { return V; }
+   std::vector<int> dom_ptr_host() const { return h_dom_ptr; }
+   std::vector<int> dom_rows_host() const { return dom_rows.to_host(); }
+   SchwarzParams prm;
+   int           n = 0, n_ext = 0, V = 1, longest_row = 0, global_rows = 0;
+   long long     nnz_A = 0;
+   double        setup_ms[4] = {0, 0, 0, 0}; // expansion, extraction, symbolic, numeric (host wall time, device synced)
+
+ private:
+   Ilu              F;
+   bool             identity = true;   // overlap adds no row: the extended numbering is the operator's own
+   std::vector<int> h_dom_ptr;         // V + 1
+   DArray<int>      dom_rows;          // n_ext: global row of every extended position (block after block, ascending inside a block)
+   DArray<int>      own_pos;           // n: position of row i in the subdomain of the block that owns it
+   DArray<int>      copy_ptr, copy_pos; // n + 1 / n_ext: the positions that hold row i, ascending subdomain
+   DArray<double>   r_ext, y_ext;
+};
+void schwarz_solve(Schwarz &S, const DCsr &A, const double *b, double *x, bool zero_guess, DArray<double> &r, DArray<double> &c);
 
 // PCG <-> preconditioner: a V-cycle from a zero guess that opens with the Jacobi sweep z0 = dinv .* r on level 0 lets its caller do
 // that multiplication where r is produced (PCG's update kernel: one pass over r and one launch less per iteration).  Thread-local,

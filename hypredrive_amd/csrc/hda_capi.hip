@@ -25,6 +25,7 @@ struct hda_amg_s {
    std::unique_ptr<Amg>                    owned_amg;
    std::unique_ptr<Ilu>                    ilu; // handle made by hda_ilu_create: the preconditioner is one ILU solve
    std::unique_ptr<Mgr>                    mgr; // handle made by hda_mgr_create: the preconditioner is one MGR solve
+   std::unique_ptr<Schwarz>                schwarz; // handle made by hda_schwarz_create: one Schwarz solve (work vectors: ilu_r / ilu_c)
    DArray<double>                          ilu_r, ilu_c;
    hda_csr_t                               A = nullptr;
    std::vector<std::unique_ptr<hda_csr_s>> views;
@@ -760,6 +761,80 @@ extern "C" int hda_ilu_blocks(hda_amg_t h, int level)
    if (!h->amg || level >= h->amg->num_levels() || !h->amg->level(level).ilu) return 0;
    return h->amg->level(level).ilu->blocks_used();
 }
+// "preconditioner: schwarz" (reference src/internal/schwarz.c): RAS / AS with ILU(k) subdomain solves (hda_schwarz.hip)
+extern "C" int hda_schwarz_create(hda_csr_t A, int variant, int overlap, int fill, int blocks, const int64_t *block_part, int max_iter,
+                                  double weight, hda_amg_t *out)
+{
+   HDA_TRY
+   HDA_REQUIRE(A && out, "hda_schwarz_create: null argument");
+   auto h     = std::make_unique<hda_amg_s>();
+   h->A       = A;
+   h->schwarz = std::make_unique<Schwarz>();
+   SchwarzParams p;
+   p.variant = variant; p.overlap = overlap; p.fill = fill; p.max_iter = max_iter; p.weight = weight;
+   p.blocks  = blocks;
+   if (block_part && blocks > 1) p.block_part.assign(block_part, block_part + blocks + 1);
+   h->schwarz->setup(A->get(), p);
+   *out = h.release();
+   HDA_CATCH
+}
+extern "C" int hda_schwarz_domains(hda_amg_t h, int *V, int *dom_ptr, int *dom_rows)
+{
+   HDA_TRY
+   HDA_REQUIRE(h && h->schwarz, "not a Schwarz handle");
+   const Schwarz &S = *h->schwarz;
+   if (V) *V = S.num_domains();
+   if (dom_ptr)
+   {
+      const std::vector<int> v = S.dom_ptr_host();
+      std::copy(v.begin(), v.end(), dom_ptr);
+   }
+   if (dom_rows && S.n_ext)
+   {
+      const std::vector<int> v = S.dom_rows_host();
+      std::copy(v.begin(), v.begin() + S.n_ext, dom_rows);
+   }
+   HDA_CATCH
+}
+extern "C" int hda_schwarz_info(hda_amg_t h, int64_t info[6], double setup_ms[4])
+{
+   HDA_TRY
+   HDA_REQUIRE(h && h->schwarz && info, "not a Schwarz handle");
+   const Schwarz &S = *h->schwarz;
+   info[0] = S.n_ext; info[1] = S.factors().nnz; info[2] = S.longest_row; info[3] = S.global_rows; info[4] = kSchwarzLdsRows; info[5] = S.nnz_A;
+   if (setup_ms)
+      for (int q = 0; q < 4; q++) setup_ms[q] = S.setup_ms[q];
+   HDA_CATCH
+}
+extern "C" int hda_precond_time(hda_amg_t h, int reps, double *avg_ms)
+{
+   HDA_TRY
+   HDA_REQUIRE(h && (h->ilu || h->schwarz) && avg_ms && reps > 0, "hda_precond_time: an ILU or Schwarz handle and reps > 0 are needed");
+   Context       &ctx = Context::get();
+   const DCsr    &m   = h->A->get();
+   const size_t   nv  = (size_t)std::max(std::max(m.ncols, m.nrows), 1);
+   DArray<double> b(nv), x(nv);
+   fill((int)nv, 0.5, b.data());
+   auto launch = [&]() {
+      if (h->schwarz) schwarz_solve(*h->schwarz, m, b.data(), x.data(), true, h->ilu_r, h->ilu_c);
+      else ilu_solve(*h->ilu, m, nullptr, b.data(), x.data(), true, h->ilu_r, h->ilu_c);
+   };
+   for (int w = 0; w < 3; w++) launch();
+   hipEvent_t e0, e1;
+   HDA_HIP(hipEventCreate(&e0));
+   HDA_HIP(hipEventCreate(&e1));
+   HDA_HIP(hipEventRecord(e0, ctx.stream));
+   for (int r = 0; r < reps; r++) launch();
+   HDA_HIP(hipEventRecord(e1, ctx.stream));
+   HDA_HIP(hipEventSynchronize(e1));
+   float ms = 0.f;
+   HDA_HIP(hipEventElapsedTime(&ms, e0, e1));
+   HDA_HIP(hipEventDestroy(e0));
+   HDA_HIP(hipEventDestroy(e1));
+   *avg_ms = ms / reps;
+   gs_free_check();
+   HDA_CATCH
+}
 // "preconditioner: mgr" (reference src/internal/mgr.c): multigrid reduction by dof labels
 extern "C" int hda_mgr_create(hda_csr_t A, const int *labels, int nlevels, const hda_mgr_level_params *levels,
                               const hda_amg_params *coarsest_amg, int max_iter, hda_amg_t *out)
@@ -856,6 +931,15 @@ extern "C" int hda_ilu_factors(hda_amg_t h, int level, hda_csr_t *out)
 {
    HDA_TRY
    const Ilu *F = nullptr;
+   if (level < 0 && h->schwarz)
+   { // the block-diagonal factors of all subdomains, extended numbering
+      auto v      = std::make_unique<hda_csr_s>();
+      v->borrowed = true;
+      v->ref      = &h->schwarz->factors();
+      *out        = v.get();
+      h->views.push_back(std::move(v));
+      return HDA_OK;
+   }
    if (level < 0) F = h->ilu.get();
    else
    {
@@ -929,6 +1013,16 @@ extern "C" int hda_amg_vcycle(hda_amg_t h, const double *b, double *x)
       gs_free_check();
       return HDA_OK;
    }
+   if (h->schwarz)
+   { // one application of the Schwarz preconditioner from a zero guess
+      const DCsr    &m = h->A->get();
+      DArray<double> db, dx((size_t)std::max(std::max(m.ncols, m.nrows), 1));
+      db.upload(b, (size_t)m.nrows);
+      schwarz_solve(*h->schwarz, m, db.data(), dx.data(), true, h->ilu_r, h->ilu_c);
+      dx.download(x, (size_t)m.nrows);
+      gs_free_check();
+      return HDA_OK;
+   }
    if (h->ilu)
    { // one application of the ILU preconditioner from a zero guess
       const DCsr    &m = h->A->get();
@@ -965,6 +1059,11 @@ static int run_krylov(int kind, hda_csr_t A, hda_amg_t amg, const hda_krylov_par
    if (amg && amg->mgr)
       M = [amg, &m](const double *r, double *z, int slot) {
          amg->mgr->solve(r, z, true);
+         if (slot >= 0) dot(m.nrows, r, z, slot);
+      };
+   else if (amg && amg->schwarz)
+      M = [amg, &m](const double *r, double *z, int slot) {
+         schwarz_solve(*amg->schwarz, m, r, z, true, amg->ilu_r, amg->ilu_c);
          if (slot >= 0) dot(m.nrows, r, z, slot);
       };
    else if (amg && amg->ilu)

@@ -48,7 +48,7 @@ struct hypre_IJMatrix_struct {
    bool assemble_csr(const long long *indptr, const long long *cols, const double *data);
 };
 
-enum hda_solver_kind { HDA_SOLVER_PCG = 1, HDA_SOLVER_GMRES = 2, HDA_SOLVER_AMG = 3, HDA_SOLVER_ILU = 4, HDA_SOLVER_FGMRES = 5, HDA_SOLVER_BICGSTAB = 6, HDA_SOLVER_MGR = 7 };
+enum hda_solver_kind { HDA_SOLVER_PCG = 1, HDA_SOLVER_GMRES = 2, HDA_SOLVER_AMG = 3, HDA_SOLVER_ILU = 4, HDA_SOLVER_FGMRES = 5, HDA_SOLVER_BICGSTAB = 6, HDA_SOLVER_MGR = 7, HDA_SOLVER_SCHWARZ = 8 };
 
 namespace hda {
 // addresses of the live solver objects THIS library created: an opaque HYPRE_Solver a caller installs with
@@ -82,6 +82,11 @@ struct hypre_Solver_struct {
    hda::IluParams            ilup;
    int                       ilu_type = 0, ilu_fill = 0, ilu_reordering = 0; // checked at Setup: bj-iluk / 0 / 0 only
    hda::DArray<double>       ilu_r, ilu_c;
+   // HYPRE_Schwarz* handle: what the setters recorded (hypre's numbering: variant 10 ras-iluk, 11 as-iluk, ...), checked at Setup
+   std::unique_ptr<hda::Schwarz> schwarz;
+   int                           sw_variant = 0, sw_overlap = 1, sw_domain_type = 2, sw_num_functions = 1, sw_nonsymm = 0, sw_local_solver = 0,
+                                 sw_fill = 0, sw_max_iter = 1, sw_print_level = 0, sw_logging = 0;
+   double                        sw_weight = 1.0, sw_tol = 0.0;
    // HYPRE_MGR* handle: what the setters recorded (hypre's per-level arrays, copied), built at Setup
    std::unique_ptr<hda::Mgr>     mgr;
    int                           mgr_block_size = 0, mgr_levels = 0, mgr_max_iter = 1, mgr_cycle = 1, mgr_frelax_cycle = 1, mgr_gsmooth_cycle = 1;
@@ -100,6 +105,9 @@ struct hypre_Solver_struct {
 namespace hda {
 // what a HYPREDRV object holds (defined in hda_hypredrv.hip): level-0 operator, its halo plan, device rhs, hierarchy
 bool hypredrv_peek(void *hypredrv, const DCsr **A, const HaloPlan **halo, const double **rhs, Amg **amg);
+// Schwarz selections (hypre's numbers, reference src/internal/schwarz.c:48-66): the reason why this one is not built, empty = built
+std::string schwarz_refusal(int variant, int local_solver, int overlap, int fill, int max_iter, double tol, int num_functions,
+                            int domain_type, int nonsymm);
 // error text of the last failed HYPRE_* call (HYPRE_GetError returns the code)
 const std::string &hypre_last_error();
 int                hypre_set_error(int code, const std::string &msg);

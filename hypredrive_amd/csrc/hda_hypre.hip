@@ -1492,6 +1492,107 @@ extern "C" HYPRE_Int HYPRE_ILUSolve(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_
 HY_GETTER(HYPRE_ILUGetNumIterations, HYPRE_Int, s->amg_iters)
 HY_GETTER(HYPRE_ILUGetFinalRelativeResidualNorm, HYPRE_Real, s->amg_rel)
 
+// ------------------------------------------------------------------------ Schwarz
+// HYPRE_Schwarz* as driven by hypredrv_SchwarzCreate (reference src/internal/schwarz.c:82-96).  Built (hda_schwarz.hip): variants 10
+// (ras-iluk) and 11 (as-iluk) with ILU(k) subdomain solves on one rank; everything else is refused by name at Setup.
+namespace hda {
+std::string schwarz_refusal(int variant, int local_solver, int overlap, int fill, int max_iter, double tol, int num_functions, int domain_type,
+                            int nonsymm)
+{
+   static const std::pair<int, const char *> names[] = {{0, "mp"}, {1, "ad"}, {2, "par-ad"}, {3, "par-mp"}, {4, "mp-fw"}, {10, "ras-iluk"},
+                                                        {11, "as-iluk"}, {20, "ras-ilut"}, {21, "as-ilut"}, {30, "ras-amg"}, {31, "as-amg"},
+                                                        {40, "ras-spdirect"}, {41, "as-spdirect"}};
+   static const char *solvers[] = {"iluk", "ilut", "amg", "spdirect"};
+   if (variant != 10 && variant != 11)
+   {
+      std::string nm = std::to_string(variant);
+      for (auto &q : names)
+         if (q.first == variant) nm = std::string("'") + q.second + "' (" + std::to_string(variant) + ")";
+      return "Schwarz: variant " + nm + " is not implemented on MI355X; ras-iluk (10) and as-iluk (11) are";
+   }
+   if (local_solver != 0)
+      return std::string("Schwarz: local_solver_type '") + (local_solver >= 0 && local_solver < 4 ? solvers[local_solver] : "?") +
+             "' contradicts variant " + (variant == 10 ? "ras-iluk" : "as-iluk") + ", whose subdomain solver is iluk";
+   if (tol != 0.0) return "Schwarz: tolerance != 0 (a residual test inside the preconditioner) is not implemented; max_iter fixed iterations are";
+   if (num_functions != 1) return "Schwarz: num_functions " + std::to_string(num_functions) + " is not implemented (1 only)";
+   if (domain_type != 2) return "Schwarz: domain_type " + std::to_string(domain_type) + " is not implemented (2, the default: one subdomain per row block, only)";
+   if (nonsymm != 0) return "Schwarz: use_nonsymm " + std::to_string(nonsymm) + " is not implemented (0 only)";
+   if (overlap < 0) return "Schwarz: overlap must be >= 0";
+   if (fill < 0) return "Schwarz: iluk_level_of_fill must be >= 0";
+   if (max_iter < 1) return "Schwarz: max_iter must be >= 1";
+   return std::string();
+}
+} // namespace hda
+
+extern "C" HYPRE_Int HYPRE_SchwarzCreate(HYPRE_Solver *solver)
+{
+   if (!solver) return hypre_set_error(HYPRE_ERROR_ARG, "HYPRE_SchwarzCreate: null output");
+   auto *s = new hypre_Solver_struct();
+   s->kind = HDA_SOLVER_SCHWARZ;
+   *solver = s;
+   return 0;
+}
+// (precon.c:138-154 calls this for whatever handle its table holds: NULL is fine, a handle of another kind is not a Schwarz handle)
+extern "C" HYPRE_Int HYPRE_SchwarzDestroy(HYPRE_Solver s)
+{
+   if (!s) return 0;
+   if (!is_live_solver(s) || s->kind != HDA_SOLVER_SCHWARZ) return hypre_set_error(HYPRE_ERROR_ARG, "HYPRE_SchwarzDestroy: not a Schwarz handle");
+   return HYPRE_BoomerAMGDestroy(s);
+}
+HY_SETTER(HYPRE_SchwarzSetVariant, HYPRE_Int, s->sw_variant = v)
+HY_SETTER(HYPRE_SchwarzSetOverlap, HYPRE_Int, s->sw_overlap = v)
+HY_SETTER(HYPRE_SchwarzSetDomainType, HYPRE_Int, s->sw_domain_type = v)
+HY_SETTER(HYPRE_SchwarzSetRelaxWeight, HYPRE_Real, s->sw_weight = v)
+HY_SETTER(HYPRE_SchwarzSetNumFunctions, HYPRE_Int, s->sw_num_functions = v)
+HY_SETTER(HYPRE_SchwarzSetNonSymm, HYPRE_Int, s->sw_nonsymm = v)
+HY_SETTER(HYPRE_SchwarzSetLocalSolverType, HYPRE_Int, s->sw_local_solver = v)
+HY_SETTER(HYPRE_SchwarzSetILUKLevelOfFill, HYPRE_Int, s->sw_fill = v)
+HY_SETTER(HYPRE_SchwarzSetILUTMaxNnzPerRow, HYPRE_Int, (void)v) // threshold variants only (refused at Setup by their variant)
+HY_SETTER(HYPRE_SchwarzSetILUTDroptol, HYPRE_Real, (void)v)    // threshold variants only
+HY_SETTER(HYPRE_SchwarzSetMaxIter, HYPRE_Int, s->sw_max_iter = v)
+HY_SETTER(HYPRE_SchwarzSetTol, HYPRE_Real, s->sw_tol = v)
+HY_SETTER(HYPRE_SchwarzSetPrintLevel, HYPRE_Int, s->sw_print_level = v)
+HY_SETTER(HYPRE_SchwarzSetLogging, HYPRE_Int, s->sw_logging = v) // (nothing is logged beyond the print_level line)
+
+extern "C" HYPRE_Int HYPRE_SchwarzSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector, HYPRE_ParVector)
+{
+   HY_TRY
+   HDA_REQUIRE(s && is_live_solver(s) && s->kind == HDA_SOLVER_SCHWARZ, "SchwarzSetup: not a Schwarz handle");
+   const std::string why = schwarz_refusal(s->sw_variant, s->sw_local_solver, s->sw_overlap, s->sw_fill, s->sw_max_iter, s->sw_tol,
+                                           s->sw_num_functions, s->sw_domain_type, s->sw_nonsymm);
+   if (!why.empty()) throw Error(why);
+   HDA_REQUIRE(Comm::world().size == 1, "Schwarz: a world of more than one rank is not implemented (subdomains across row partitions need off-rank rows); "
+                                        "one rank with HDA_BLOCKS row blocks is");
+   if (!have_device()) throw Error("no HIP device visible: the MI355X solve path has no CPU fallback");
+   HDA_REQUIRE(A && A->assembled, "SchwarzSetup needs an assembled matrix");
+   SchwarzParams p;
+   p.variant = s->sw_variant - 10; p.overlap = s->sw_overlap; p.fill = s->sw_fill; p.max_iter = s->sw_max_iter; p.weight = s->sw_weight;
+   // one subdomain per rank is hypre's picture; on one GPU the row blocks play the ranks (HDA_BLOCKS = V, 0 = the setup's choice), as for ILU
+   p.blocks  = getenv("HDA_BLOCKS") ? std::max(atoi(getenv("HDA_BLOCKS")), 0) : 1;
+   s->schwarz = std::make_unique<Schwarz>();
+   s->schwarz->setup(A->A, p);
+   const Schwarz &S = *s->schwarz;
+   if (S.V > 1 && !getenv("HDA_QUIET"))
+      fprintf(stderr, "[hypredrv_amd] Schwarz: %d row blocks (HDA_BLOCKS): one subdomain per block, as the reference has one per rank on %d ranks\n", S.V, S.V);
+   if (s->sw_print_level >= 1)
+      printf("Schwarz (%s): %d subdomains, overlap %d, N_ext / n = %.3f, ILU(%d), nnz(LU) / nnz(A) = %.3f\n", s->sw_variant == 10 ? "ras-iluk" : "as-iluk",
+             S.V, p.overlap, S.n ? (double)S.n_ext / S.n : 1.0, p.fill, S.nnz_A ? (double)S.factors().nnz / (double)S.nnz_A : 1.0);
+   hda_register_precond_veclen((size_t)std::max(A->A.ncols, A->A.nrows));
+   HY_CATCH
+}
+
+extern "C" HYPRE_Int HYPRE_SchwarzSolve(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
+{
+   HY_NEED_DEVICE;
+   HY_TRY
+   HDA_REQUIRE(s && s->schwarz, "SchwarzSolve before SchwarzSetup");
+   x->ensure_device();
+   PrecondHints &h = precond_hints();
+   schwarz_solve(*s->schwarz, A->A, b->data(), x->data(), h.zero_guess, s->ilu_r, s->ilu_c);
+   s->amg_iters = std::max(s->sw_max_iter, 1);
+   HY_CATCH
+}
+
 // ------------------------------------------------------------------------ MGR
 // HYPRE_MGR* as driven by hypredrv_MGRCreate (reference src/internal/mgr.c:3782-3808 base settings, per-level
 // arrays after :3820).  hypre's calling convention is kept: C points of every reduction level by dof label
@@ -1800,7 +1901,6 @@ HY_REFUSED(HYPRE_ParCSRGMRESSetRefSolution, (HYPRE_Solver, HYPRE_ParVector), "er
 HY_FOREIGN_DESTROY(HYPRE_FSAIDestroy, "FSAI")
 HY_FOREIGN_DESTROY(HYPRE_AMSDestroy, "AMS")
 HY_FOREIGN_DESTROY(HYPRE_ADSDestroy, "ADS")
-HY_FOREIGN_DESTROY(HYPRE_SchwarzDestroy, "Schwarz")
 #undef HY_FOREIGN_DESTROY
 
 // HYPRE_ParVector{Create,Initialize,Destroy} (amg.c:557, precon.c:770-783): a ParVector IS this library's IJ vector (HYPRE.h);

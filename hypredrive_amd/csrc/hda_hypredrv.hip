@@ -1589,6 +1589,7 @@ static HYPRE_Int PreconSetupDispatch(HYPRE_Solver cookie, HYPRE_Matrix A, HYPRE_
    hypredrv_struct *h = ((PreconCookie *)(void *)cookie)->self;
    annotate(h, "prec", true);
    HYPRE_Int ierr = (h->precon->kind == HDA_SOLVER_ILU)   ? HYPRE_ILUSetup(h->precon, A, b, x)
+                    : (h->precon->kind == HDA_SOLVER_SCHWARZ) ? HYPRE_SchwarzSetup(h->precon, A, b, x)
                     : (h->precon->kind == HDA_SOLVER_MGR) ? HYPRE_MGRSetup(h->precon, A, b, x)
                                                           : HYPRE_BoomerAMGSetup(h->precon, A, b, x);
    if (hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
@@ -1601,6 +1602,7 @@ static HYPRE_Int PreconSolveDispatch(HYPRE_Solver cookie, HYPRE_Matrix A, HYPRE_
 {
    hypredrv_struct *h = ((PreconCookie *)(void *)cookie)->self;
    return (h->precon->kind == HDA_SOLVER_ILU)   ? HYPRE_ILUSolve(h->precon, A, b, x)
+          : (h->precon->kind == HDA_SOLVER_SCHWARZ) ? HYPRE_SchwarzSolve(h->precon, A, b, x)
           : (h->precon->kind == HDA_SOLVER_MGR) ? HYPRE_MGRSolve(h->precon, A, b, x)
                                                 : HYPRE_BoomerAMGSolve(h->precon, A, b, x);
 }
@@ -1624,6 +1626,28 @@ static void ilu_create(const IluArgs &a, HYPRE_Solver *out)
    const bool schur = a.type == 10 || a.type == 11 || a.type == 20 || a.type == 21 || a.type == 40 || a.type == 41 || a.type == 50;
    if (schur) HYPRE_ILUSetSchurMaxIter(p, a.schur_max_iter);
    if (a.type == 20 || a.type == 21) HYPRE_ILUSetNSHDropThreshold(p, a.nsh_droptol);
+   *out = p;
+}
+
+// hypredrv_SchwarzCreate (reference src/internal/schwarz.c:77-99): same setter sequence
+static void schwarz_create(const SchwarzArgs &a, HYPRE_Solver *out)
+{
+   HYPRE_Solver p = nullptr;
+   HYPRE_SchwarzCreate(&p);
+   HYPRE_SchwarzSetVariant(p, a.variant);
+   HYPRE_SchwarzSetOverlap(p, a.overlap);
+   HYPRE_SchwarzSetDomainType(p, a.domain_type);
+   HYPRE_SchwarzSetRelaxWeight(p, a.relax_weight);
+   HYPRE_SchwarzSetNumFunctions(p, a.num_functions);
+   HYPRE_SchwarzSetNonSymm(p, a.use_nonsymm);
+   HYPRE_SchwarzSetLocalSolverType(p, a.local_solver_type);
+   HYPRE_SchwarzSetILUKLevelOfFill(p, a.iluk_level_of_fill);
+   HYPRE_SchwarzSetILUTMaxNnzPerRow(p, a.ilut_max_nnz_row);
+   HYPRE_SchwarzSetILUTDroptol(p, a.ilut_droptol);
+   HYPRE_SchwarzSetMaxIter(p, a.max_iter);
+   HYPRE_SchwarzSetTol(p, a.tolerance);
+   HYPRE_SchwarzSetPrintLevel(p, a.print_level);
+   HYPRE_SchwarzSetLogging(p, a.logging);
    *out = p;
 }
 
@@ -1919,10 +1943,24 @@ extern "C" uint32_t HYPREDRV_PreconCreate(HYPREDRV_t h)
       consume_hypre_errors();
       return g_err;
    }
+   if (p.method == 6)
+   { // what is not built is refused here, by name, not at parse: the reference's own inputs with the other variants keep parsing
+      const SchwarzArgs &a   = p.schwarz;
+      const std::string  why = schwarz_refusal(a.variant, a.local_solver_type, a.overlap, a.iluk_level_of_fill, a.max_iter, a.tolerance,
+                                               a.num_functions, a.domain_type, a.use_nonsymm);
+      if (!why.empty()) return err_set(ERR_INVALID_PRECON | HYPREDRV_ERROR_UNSUPPORTED_AMD, why);
+      if (Comm::world().size > 1)
+         return err_set(ERR_INVALID_PRECON | HYPREDRV_ERROR_UNSUPPORTED_AMD,
+                        "Schwarz: a world of more than one rank is not implemented (subdomains across row partitions need off-rank rows); one rank "
+                        "with HDA_BLOCKS row blocks is");
+      schwarz_create(a, &h->precon);
+      consume_hypre_errors();
+      return g_err;
+   }
    if (p.method == 1) return mgr_create(h, p.mgr);
    if (p.method != 0)
       return err_set(ERR_INVALID_PRECON | HYPREDRV_ERROR_UNSUPPORTED_AMD,
-                     "preconditioner '" + p.method_name + "' is not implemented on MI355X yet (BoomerAMG, ILU and MGR only)");
+                     "preconditioner '" + p.method_name + "' is not implemented on MI355X yet (BoomerAMG, ILU, MGR and Schwarz only)");
    amg_create(p.amg, &h->precon);
    // hypredrv_AMGSetDofFunc (reference src/internal/amg.c:792-862): the dofmap names the function of
    // every local unknown when its labels fit [0, num_functions); otherwise hypre's interleaved default
@@ -2300,6 +2338,7 @@ extern "C" uint32_t HYPREDRV_PreconApply(HYPREDRV_t h, HYPRE_Vector b, HYPRE_Vec
    API_TRY
    if (!h->precon || !h->precon_is_setup) return err_set(ERR_INVALID_PRECON, "PreconApply requires a set-up preconditioner");
    if (h->precon->kind == HDA_SOLVER_ILU) HYPRE_ILUSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
+   else if (h->precon->kind == HDA_SOLVER_SCHWARZ) HYPRE_SchwarzSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
    else if (h->precon->kind == HDA_SOLVER_MGR) HYPRE_MGRSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
    else HYPRE_BoomerAMGSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
    consume_hypre_errors();

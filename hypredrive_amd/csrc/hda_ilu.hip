@@ -267,11 +267,40 @@ void Ilu::setup(const DCsr &A, const IluParams &p)
       sort_rows(LU);
       k_ilu_diag<<<ceil_div(n, 256), 256, 0, STREAM>>>(n, LU.rowptr.data(), LU.col.data(), diag.data());
    }
+   HDA_REQUIRE(!(factor_and_plan() & 4), "ILU(0): zero pivot");
+}
+
+// the internal entry behind a caller that brings its own pattern (the Schwarz subdomain solves, hda_schwarz.hip): P holds the
+// pattern of the factors, column-sorted, every row with its diagonal entry, the operator's values scattered in and zeros at the
+// fill positions; part = the row starts of its diagonal blocks (empty or one block: none).  Returns the factorisation's flags
+// (bit 2: a zero pivot) instead of throwing, so that the caller can name what it factorised.
+int Ilu::setup_pattern(DCsr &&P, const IluParams &p, const std::vector<int> &part)
+{
+   prm          = p;
+   prm.lower_it = std::max(p.lower_it, 1);
+   prm.upper_it = std::max(p.upper_it, 1);
+   LU           = std::move(P);
+   const int n  = LU.nrows;
+   diag.alloc((size_t)std::max(n, 1));
+   bpart = part;
+   if (bpart.size() <= 2) bpart.clear();
+   bplan = GsPlan();
+   if (n) k_ilu_diag<<<ceil_div(n, 256), 256, 0, STREAM>>>(n, LU.rowptr.data(), LU.col.data(), diag.data());
+   return factor_and_plan();
+}
+
+// numeric factorisation of LU on its dependency levels, then what the substitutions need; returns the flags (bit 2: zero pivot)
+int Ilu::factor_and_plan()
+{
+   const int   n  = LU.nrows;
+   const int   nb = bpart.empty() ? 0 : (int)bpart.size() - 1;
+   int         f  = 0;
+   DArray<int> flag(1);
    build_gs_plan(LU, plan);
    flag.zero();
    run_levels<OP_FACTOR>(LU, plan, diag.data(), nullptr, flag.data());
    flag.download(&f, 1);
-   HDA_REQUIRE(!(f & 4), "ILU(0): zero pivot");
+   if (f & 4) return f;
    work.alloc((size_t)std::max(n, 1) * 2);
    Ls = DCsr();
    Us = DCsr();
@@ -308,6 +337,7 @@ void Ilu::setup(const DCsr &A, const IluParams &p)
       spmv_prepare(Ls);
       spmv_prepare(Us);
    }
+   return f;
 }
 
 // z = U^{-1} L^{-1} r   (r and z may not alias)

@@ -442,6 +442,23 @@ static void ilu_fields(Ctx &c, YNode &sec, IluArgs &a)
                  {"nsh_droptol", nullptr, &a.nsh_droptol, nullptr}, {"tolerance", nullptr, &a.tolerance, nullptr}});
 }
 
+// Schwarz_FIELDS and the name maps of hypredrv_SchwarzGetValidValues (reference src/internal/schwarz.c:20-34, :48-66).  Every name
+// parses; what is not built is refused at HYPREDRV_PreconCreate.
+static const StrMap kSchwarzVariant = {{"mp", 0}, {"ad", 1}, {"par-ad", 2}, {"par-mp", 3}, {"mp-fw", 4}, {"ras-iluk", 10}, {"as-iluk", 11},
+                                       {"ras-ilut", 20}, {"as-ilut", 21}, {"ras-amg", 30}, {"as-amg", 31}, {"ras-spdirect", 40}, {"as-spdirect", 41}};
+static const StrMap kSchwarzLocal = {{"iluk", 0}, {"ilut", 1}, {"amg", 2}, {"spdirect", 3}, {"superlu", 3}};
+static void schwarz_fields(Ctx &c, YNode &sec, SchwarzArgs &a)
+{
+   apply_fields(c, sec,
+                {{"variant", &a.variant, nullptr, &kSchwarzVariant}, {"overlap", &a.overlap, nullptr, nullptr},
+                 {"domain_type", &a.domain_type, nullptr, nullptr}, {"num_functions", &a.num_functions, nullptr, nullptr},
+                 {"use_nonsymm", &a.use_nonsymm, nullptr, &kOnOff}, {"local_solver_type", &a.local_solver_type, nullptr, &kSchwarzLocal},
+                 {"iluk_level_of_fill", &a.iluk_level_of_fill, nullptr, nullptr}, {"ilut_max_nnz_row", &a.ilut_max_nnz_row, nullptr, nullptr},
+                 {"max_iter", &a.max_iter, nullptr, nullptr}, {"print_level", &a.print_level, nullptr, nullptr},
+                 {"logging", &a.logging, nullptr, nullptr}, {"relax_weight", nullptr, &a.relax_weight, nullptr},
+                 {"ilut_droptol", nullptr, &a.ilut_droptol, nullptr}, {"tolerance", nullptr, &a.tolerance, nullptr}});
+}
+
 // mgr block (reference src/internal/mgr.c:1736-1870; value maps :1553-1721)
 static const StrMap kMgrInterp = {{"injection", 0}, {"l1-jacobi", 1}, {"jacobi", 2}, {"classical-mod", 3}, {"approx-inv", 4}, {"blk-jacobi", 12},
                                   {"blk-rowlump", 13}, {"blk-rowsum", 13}, {"blk-absrowsum", 14}};
@@ -944,6 +961,7 @@ static void parse_precon_body(Ctx &c, YNode &node, std::vector<PreconArgs> &vari
             if (p.method == 0) amg_fields(c, *item, v.amg);
             else if (p.method == 2) ilu_fields(c, *item, v.ilu);
             else if (p.method == 1) mgr_fields(c, *item, v.mgr);
+            else if (p.method == 6) schwarz_fields(c, *item, v.schwarz);
             variants.push_back(v);
          }
       }
@@ -952,6 +970,7 @@ static void parse_precon_body(Ctx &c, YNode &node, std::vector<PreconArgs> &vari
          if (p.method == 0) amg_fields(c, *ch, p.amg);
          else if (p.method == 2) ilu_fields(c, *ch, p.ilu);
          else if (p.method == 1) mgr_fields(c, *ch, p.mgr);
+         else if (p.method == 6) schwarz_fields(c, *ch, p.schwarz);
          variants.push_back(p);
       }
    }

@@ -73,6 +73,11 @@ struct IluArgs { // ILU_args, defaults of src/internal/ilu.c:15-28
           upper_jac_iters = 5, max_row_nnz = 200, schur_max_iter = 3;
    double droptol = 1.0e-2, nsh_droptol = 1.0e-2, tolerance = 0.0;
 };
+struct SchwarzArgs { // Schwarz_args, defaults of src/internal/schwarz.c:20-34 (hypre's numbers: variant 10 ras-iluk, 11 as-iluk; local solver 0 iluk)
+   int    variant = 10, overlap = 1, domain_type = 2, num_functions = 1, use_nonsymm = 0, local_solver_type = 0, iluk_level_of_fill = 0,
+          ilut_max_nnz_row = 1000, max_iter = 1, print_level = 0, logging = 0;
+   double relax_weight = 1.0, ilut_droptol = 1.0e-2, tolerance = 0.0;
+};
 struct AmgArgs { // AMG_args, GPU-branch defaults of src/internal/amg.c:120-238
    int    max_iter = 1, print_level = 0;
    double tolerance = 0.0;
@@ -144,6 +149,7 @@ struct PreconArgs {
    AmgArgs     amg;
    IluArgs     ilu;
    MgrArgs     mgr;
+   SchwarzArgs schwarz;
 };
 // preconditioner.reuse (reference src/internal/precon_reuse.c:2280-2567): the static policy
 struct ReuseArgs {

@@ -359,7 +359,27 @@ HYPRE_Int HYPRE_ParCSRGMRESSetRefSolution(HYPRE_Solver solver, HYPRE_ParVector x
 HYPRE_Int HYPRE_FSAIDestroy(HYPRE_Solver solver);
 HYPRE_Int HYPRE_AMSDestroy(HYPRE_Solver solver);
 HYPRE_Int HYPRE_ADSDestroy(HYPRE_Solver solver);
+/* ---- Schwarz as hypredrv_SchwarzCreate drives it (src/internal/schwarz.c:82-96).  Built: variants 10 (ras-iluk) and 11 (as-iluk) with
+ * local solver iluk on one rank (row blocks: HDA_BLOCKS, as for ILU); every other selection is refused by name at Setup.  Destroy
+ * accepts NULL and Schwarz handles only. */
+HYPRE_Int HYPRE_SchwarzCreate(HYPRE_Solver *solver);
 HYPRE_Int HYPRE_SchwarzDestroy(HYPRE_Solver solver);
+HYPRE_Int HYPRE_SchwarzSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_SchwarzSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_SchwarzSetVariant(HYPRE_Solver solver, HYPRE_Int variant);
+HYPRE_Int HYPRE_SchwarzSetOverlap(HYPRE_Solver solver, HYPRE_Int overlap);
+HYPRE_Int HYPRE_SchwarzSetDomainType(HYPRE_Solver solver, HYPRE_Int domain_type);
+HYPRE_Int HYPRE_SchwarzSetRelaxWeight(HYPRE_Solver solver, HYPRE_Real relax_weight);
+HYPRE_Int HYPRE_SchwarzSetNumFunctions(HYPRE_Solver solver, HYPRE_Int num_functions);
+HYPRE_Int HYPRE_SchwarzSetNonSymm(HYPRE_Solver solver, HYPRE_Int use_nonsymm);
+HYPRE_Int HYPRE_SchwarzSetLocalSolverType(HYPRE_Solver solver, HYPRE_Int local_solver_type);
+HYPRE_Int HYPRE_SchwarzSetILUKLevelOfFill(HYPRE_Solver solver, HYPRE_Int level_of_fill);
+HYPRE_Int HYPRE_SchwarzSetILUTMaxNnzPerRow(HYPRE_Solver solver, HYPRE_Int max_nnz_row);
+HYPRE_Int HYPRE_SchwarzSetILUTDroptol(HYPRE_Solver solver, HYPRE_Real droptol);
+HYPRE_Int HYPRE_SchwarzSetMaxIter(HYPRE_Solver solver, HYPRE_Int max_iter);
+HYPRE_Int HYPRE_SchwarzSetTol(HYPRE_Solver solver, HYPRE_Real tol);
+HYPRE_Int HYPRE_SchwarzSetPrintLevel(HYPRE_Solver solver, HYPRE_Int print_level);
+HYPRE_Int HYPRE_SchwarzSetLogging(HYPRE_Solver solver, HYPRE_Int logging);
 /* amg.c:557, precon.c:770-783: a ParVector is this library's IJ vector; partitioning = {first row, one past the last} of the
  * calling rank, NULL = hypre's even split */
 HYPRE_Int HYPRE_ParVectorCreate(MPI_Comm comm, HYPRE_BigInt global_size, HYPRE_BigInt *partitioning, HYPRE_ParVector *vector);

@@ -184,6 +184,20 @@ int hda_ilu_create(hda_csr_t A, int max_iter, int tri_solve, int lower_it, int u
 int hda_ilu_create_blocks(hda_csr_t A, int max_iter, int tri_solve, int lower_it, int upper_it, int blocks, const int64_t *block_part,
                           hda_amg_t *out);
 int hda_ilu_blocks(hda_amg_t h, int level); /* row blocks in use: level < 0 a handle of hda_ilu_create*, else that AMG level's smoother */
+/* "preconditioner: schwarz" (reference src/internal/schwarz.c; variants ras-iluk / as-iluk): overlapping Schwarz on V contiguous row
+ * blocks (blocks / block_part as hda_ilu_create_blocks) grown by `overlap` layers of A's stored pattern, ILU(fill) of every subdomain,
+ * z = weight * (variant 0: the owner's value | variant 1: the sum over the subdomains that hold the row).  The handle is accepted by
+ * the Krylov entries and hda_amg_vcycle as an ILU handle is; hda_ilu_factors(h, -1, ..) views the block-diagonal factors in the
+ * extended numbering (subdomain after subdomain, ascending global row inside one). */
+int hda_schwarz_create(hda_csr_t A, int variant, int overlap, int fill, int blocks, const int64_t *block_part, int max_iter, double weight,
+                       hda_amg_t *out);
+/* *V = subdomains; dom_ptr (V + 1 entries) and dom_rows (N_ext entries, the global row of every extended position) may be NULL */
+int hda_schwarz_domains(hda_amg_t h, int *V, int *dom_ptr, int *dom_rows);
+/* info[0..5]: N_ext, nnz of the factors, longest factor row, rows that took the global-memory symbolic path, capacity of the symbolic
+ * kernel's LDS table (visited vertices per row), nnz of A; setup_ms (may be NULL): expansion, extraction, symbolic, numeric */
+int hda_schwarz_info(hda_amg_t h, int64_t info[6], double setup_ms[4]);
+/* average device ms of one application (zero guess, vectors resident) of a handle of hda_ilu_create* or hda_schwarz_create */
+int hda_precond_time(hda_amg_t h, int reps, double *avg_ms);
 /* "preconditioner: mgr" (reference src/internal/mgr.c; MGRlvl_args include/internal/mgr.h:132-147): multigrid reduction
  * by dof labels with BoomerAMG on the coarsest system.  labels = dofmap of A's rows.  Implemented per level:
  * prolongation injection (0) / l1-jacobi (1) / jacobi (2); restriction injection (0) / jacobi (2) / columped (14);

@@ -10,7 +10,10 @@
 
 Each runs through HYPREDRV_LinearSolverSetup / Apply like the headline and returns: iterations, ms per solve, setup, the dominant
 kernel's SURVEY 8(d) bytes / time, and `iters_match`: the same configuration on a size the oracle finishes in seconds, device
-iteration count == oracle's.  bench.py carries them as budgeted extras; `python tools/side_configs.py [mgr|ilu0] [size]` runs one."""
+iteration count == oracle's.  bench.py carries them as budgeted extras; `python tools/side_configs.py [mgr|ilu0] [size]` runs one.
+
+  schwarz N       not a BASELINE config: GMRES(30) + RAS(1)-ILU(0) / RAS(1)-ILU(1) on the N^3 Laplacian, on the row
+                  blocks HDA_BLOCKS gives: setup ms by phase, ms per application, iterations (`python tools/side_configs.py schwarz 128`)"""
 import json
 import os
 import sys
@@ -159,10 +162,42 @@ def gmres_amg_ilu0(hh, n=128, steps=3, warmup=1, oracle_n=20, with_oracle=True):
     return out
 
 
+def gmres_schwarz(hh, n=128, reps=10):
+    """GMRES(30) + RAS(1)-ILU(0) and RAS(1)-ILU(1) on the n^3 7-point Laplacian, on the row blocks HDA_BLOCKS gives (unset: one), beside
+    the no-overlap ILU(0) Schwarz and the block ILU(0) of hda_ilu_create_blocks on the same blocks.  Per configuration: setup ms (host wall
+    time, device synced) with its split by phase, device ms per application, iterations."""
+    V = max(int(os.environ.get("HDA_BLOCKS", "1")), 0)
+    A = hh.lap7(n, n, n)
+    N = n ** 3
+    b = np.ones(N)
+    kp = hh.KrylovParams.default(True)
+    out = {"what": f"GMRES(30) + Schwarz on the {n}^3 7-point Laplacian, {V} row block(s) (0 = the setup's choice)", "rows": N, "runs": []}
+    for name, make in (("block ILU(0) (hda_ilu_create_blocks)", lambda: hh.Ilu(A, blocks=V)),
+                       ("RAS(0)-ILU(0)", lambda: hh.Schwarz(A, "ras", 0, 0, V)), ("RAS(1)-ILU(0)", lambda: hh.Schwarz(A, "ras", 1, 0, V)),
+                       ("RAS(1)-ILU(1)", lambda: hh.Schwarz(A, "ras", 1, 1, V)), ("AS(1)-ILU(0)", lambda: hh.Schwarz(A, "as", 1, 0, V))):
+        make()  # the first setup of a shape also pays for the allocator
+        hh.sync()
+        t0 = time.perf_counter()
+        M = make()
+        hh.sync()
+        run = {"config": name, "setup_ms": (time.perf_counter() - t0) * 1e3, "apply_ms": hh.precond_time(M, reps)}
+        if isinstance(M, hh.Schwarz):
+            info = M.info()
+            run["setup_phases_ms"] = info.pop("setup_ms")
+            run.update(info)
+        res = hh.gmres(A, b, M, kp)
+        run.update(iters=res["iters"], converged=res["converged"], final_rel=res["final_rel"])
+        out["runs"].append(run)
+        del M
+    return out
+
+
 if __name__ == "__main__":
     import hypredrive_amd as hh
     which = sys.argv[1] if len(sys.argv) > 1 else "mgr"
-    if which == "mgr":
+    if which == "schwarz":
+        print(json.dumps(gmres_schwarz(hh, int(sys.argv[2]) if len(sys.argv) > 2 else 128)))
+    elif which == "mgr":
         print(json.dumps(gmres_mgr(hh, int(sys.argv[2]) if len(sys.argv) > 2 else 512)))
     else:
         print(json.dumps(gmres_amg_ilu0(hh, int(sys.argv[2]) if len(sys.argv) > 2 else 128)))
