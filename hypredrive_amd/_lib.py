@@ -27,6 +27,7 @@ class AmgParams(C.Structure):
                 ("smooth_num_levels", C.c_int), ("smooth_num_sweeps", C.c_int),
                 ("ilu_tri_solve", C.c_int), ("ilu_lower_it", C.c_int), ("ilu_upper_it", C.c_int),
                 ("restrict_type", C.c_int), ("restrict_strong_th", C.c_double), ("restrict_filter_th", C.c_double), ("relax_points", C.c_int),
+                ("agg_p12_pmax", C.c_int), ("agg_p12_trunc_factor", C.c_double),
                 ("agg_num_levels", C.c_int), ("agg_num_paths", C.c_int), ("agg_interp_type", C.c_int),
                 ("agg_pmax", C.c_int), ("agg_trunc_factor", C.c_double),
                 ("blocks", C.c_int), ("block_part", C.POINTER(C.c_int64)), ("struct_size", C.c_int)]
@@ -88,7 +89,7 @@ SYMBOLS = [
     "hda_pcg_iteration_bytes", "hda_memory_stats", "hda_memory_cached", "hda_memory_driver_stats", "hda_memory_trim", "hda_comm_selftest", "hda_check_row_total", "hda_ilu_create", "hda_ilu_create_blocks", "hda_ilu_blocks", "hda_ilu_factors", "hda_fgmres", "hda_bicgstab", "hda_mgr_create", "hda_mgr_matrix", "hda_mgr_blk_inverses",
     "hda_probe_add", "hda_probe_read_id", "hda_borrow_hypredrv", "hda_comm_stats", "hda_comm_name", "hda_comm_size", "hda_halo_plan_host",
     "hda_amd_partitioned_levels", "hda_amd_hierarchy_levels",
-    "hda_second_strength", "hda_coarsen_second_pass", "hda_interp_multipass", "hda_truncate_rows",
+    "hda_second_strength", "hda_coarsen_second_pass", "hda_interp_multipass", "hda_truncate_rows", "hda_interp_agg_two_stage",
     "hda_interp_mm_extpi", "hda_interp_extended", "hda_interp_mm_ext", "hda_interp_one_point", "hda_interp_standard", "hda_set_overlap", "hda_marker", "hda_relax_blocks", "hda_l1_norms_blocks", "hda_hmis_blocks", "hda_amg_blocks", "hda_amg_level_blocks",
     "hda_csr_form", "hda_spmv_mode", "hda_air_restriction",
     "hda_cljp", "hda_rs_blocks", "hda_falgout_blocks", "hda_measure_rnd",
@@ -175,6 +176,7 @@ def load():
     L.hda_coarsen_second_pass.argtypes = [vp, P(C.c_ubyte), C.c_int, C.c_uint64, C.c_int, ip]
     L.hda_interp_multipass.argtypes = [vp, P(C.c_ubyte), ip, P(vp)]
     L.hda_truncate_rows.argtypes = [vp, C.c_int, C.c_double]
+    L.hda_interp_agg_two_stage.argtypes = [vp, P(C.c_ubyte), ip, ip, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, P(vp), P(vp), P(vp)]
     L.hda_transpose.argtypes = [vp, P(vp)]
     L.hda_spgemm.argtypes = [vp, vp, P(vp)]
     L.hda_amg_create.argtypes = [P(AmgParams), vp, P(vp)]
@@ -455,6 +457,32 @@ class Csr:
         out = C.c_void_p()
         _check(load().hda_interp_multipass(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), _ip(cfa), C.byref(out)))
         return Csr(out)
+
+    def interp_agg_two_stage_parts(self, smask, cf1, cf2, plus_i=False, p12_pmax=0, p12_tf=0.0, pmax=0, tf=0.0):
+        """aggressive.prolongation_type 5 (plus_i False: mm_extended) / 6 (True: mm_extended+i): (P1, P2, P) with P = P1 P2.  cf1: the
+        splitting after the first coarsening pass, cf2: after coarsen_second_pass; P1 (n x |C1|) is truncated by p12_pmax / p12_tf,
+        P2 (|C1| x |C2|) by pmax / tf."""
+        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
+        c1 = np.ascontiguousarray(np.concatenate([cf1, np.zeros(1, np.int32)]), dtype=np.int32)
+        c2 = np.ascontiguousarray(np.concatenate([cf2, np.zeros(1, np.int32)]), dtype=np.int32)
+        o1, o2, o = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(load().hda_interp_agg_two_stage(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), _ip(c1), _ip(c2), 1 if plus_i else 0,
+                                               int(p12_pmax), float(p12_tf), int(pmax), float(tf), C.byref(o1), C.byref(o2), C.byref(o)))
+        return Csr(o1), Csr(o2), Csr(o)
+
+    def interp_agg_second_stage(self, smask, cf1, cf2, plus_i=False, pmax=0, tf=0.0):
+        """P2 alone (only the |C1| rows of the second stage are built)"""
+        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
+        c1 = np.ascontiguousarray(np.concatenate([cf1, np.zeros(1, np.int32)]), dtype=np.int32)
+        c2 = np.ascontiguousarray(np.concatenate([cf2, np.zeros(1, np.int32)]), dtype=np.int32)
+        o2 = C.c_void_p()
+        _check(load().hda_interp_agg_two_stage(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), _ip(c1), _ip(c2), 1 if plus_i else 0,
+                                               0, 0.0, int(pmax), float(tf), None, C.byref(o2), None))
+        return Csr(o2)
+
+    def interp_agg_two_stage(self, smask, cf1, cf2, plus_i=False, p12_pmax=0, p12_tf=0.0, pmax=0, tf=0.0):
+        """the product P of interp_agg_two_stage_parts"""
+        return self.interp_agg_two_stage_parts(smask, cf1, cf2, plus_i, p12_pmax, p12_tf, pmax, tf)[2]
 
     def truncate_rows(self, pmax=0, trunc_factor=0.0):
         """hypre_BoomerAMGInterpTruncation on the finished rows of this interpolation matrix, in place"""

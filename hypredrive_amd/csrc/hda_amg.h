@@ -56,7 +56,11 @@ struct AmgParams {
    int       smooth_type = 5, smooth_num_levels = 0, smooth_num_sweeps = 1;
    IluParams ilu;
    // aggressive coarsening (AMGagg_args, amg.c:160-173, 938-944; hda_amg_agg.hip): on the first agg_num_levels levels a second PMIS
-   // pass over the distance-two strength graph (>= agg_num_paths paths of length <= 2) and multipass interpolation (type 4, untruncated)
+   // pass over the distance-two strength graph (>= agg_num_paths paths of length <= 2) and multipass interpolation (type 4) or the
+   // two-stage mm-ext (5) / mm-ext+i (6) interpolation, whose first stage is truncated by agg_p12_pmax / agg_p12_trunc_factor
+   // (aggressive.P12_max_elements / P12_trunc_factor)
+   int    agg_p12_pmax = 0;
+   double agg_p12_trunc_factor = 0.0;
    int agg_num_levels = 0, agg_num_paths = 1, agg_interp_type = 4;
    int    agg_pmax = 0;           // aggressive.max_nnz_row (HYPRE_BoomerAMGSetAggPMaxElmts): 0 = no limit
    double agg_trunc_factor = 0.0; // aggressive.trunc_factor (HYPRE_BoomerAMGSetAggTruncFactor)
@@ -529,9 +533,22 @@ void amg_truncate_rows(DCsr &P, int pmax, double trunc_factor); // hypre_BoomerA
 // plus_i = false: mm-ext (type 16), the same products with s_ki := 0
 void amg_interp_mm_extpi(const DCsr &A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, DCsr &P,
                          const int *dof = nullptr, bool plus_i = true);
+// two-stage mm-ext (plus_i false, aggressive.prolongation_type 5) / mm-ext+i (true, 6) interpolation of an aggressive level (DESIGN
+// section 16): cf1 the splitting after the first coarsening pass, cf2 after the second (its C points a subset of cf1's, the others F).
+// P = P1 P2, P1 = the mm operator of cf1 truncated by the P12 pair, P2 (|C1| x |C2|) = the C1 rows of the mm operator of cf2 truncated
+// by pmax / trunc_factor; amg_interp_mm_partial builds P2 on those rows alone.  P1_out / P2_out: the stages, for the tests.
+void amg_interp_mm_partial(const DCsr &A, const unsigned char *smask, const int *cf1, const int *cf2, int pmax, double trunc_factor, bool plus_i,
+                           DCsr &P2);
+void amg_interp_agg_two_stage(const DCsr &A, const unsigned char *smask, const int *cf1, const int *cf2, bool plus_i, int p12_pmax,
+                              double p12_trunc_factor, int pmax, double trunc_factor, DCsr &P, DCsr *P1_out = nullptr, DCsr *P2_out = nullptr);
 // one-point interpolation (type 100): an F row's single entry of weight 1 towards its strong C neighbour of largest |a_ij| (the first in
 // column order among equals), no entry without a strong C neighbour; C rows identity
 void amg_interp_one_point(const DCsr &A, const unsigned char *smask, const int *cf, DCsr &P);
+// the interpolation types of the aggressive levels the setup builds (4 multipass, 5 / 6 two-stage mm-ext / mm-ext+i), their YAML
+// names (nullptr: no name), and the refusal of the others by name
+bool        amg_agg_interp_type_built(int t);
+const char *amg_agg_interp_name(int t);
+std::string amg_agg_interp_refusal(int t);
 // the prolongation types amg_interp_extpi builds, and the refusal of the others by name
 bool        amg_interp_type_built(int t);
 std::string amg_interp_refusal(int t);

@@ -422,6 +422,98 @@ __global__ __launch_bounds__(256) void k_mm_p_fill(int n, const int *__restrict_
    }
 }
 
+// ---- the same builder on a list of rows (second stage of the two-stage aggressive interpolation, aggressive types 5 / 6): thread r
+// works on row i = rows[r] of the operator and writes row r of its outputs (cnt, B, dd, P), so the products and the truncation run on
+// the listed rows alone.  The walks are those of k_mm_rows / k_mm_p_count / k_mm_p_fill statement for statement (same order of every
+// sum); k_mm_q and k_mm_fc_fill stay on all rows, since the columns of B are arbitrary F points.
+__global__ __launch_bounds__(256) void k_agg_row_list(int n, const int *__restrict__ cf, const int *__restrict__ cidx, int *__restrict__ rows)
+{
+   const int i = blockIdx.x * 256 + threadIdx.x;
+   if (i < n && cf[i] == kC) rows[cidx[i]] = i;
+}
+template <bool FILL, bool PLUSI>
+__global__ __launch_bounds__(256) void k_mm_rows_list(int nr, const int *__restrict__ rows, const int *__restrict__ rp, const int *__restrict__ cj,
+                                                      const double *__restrict__ v, const unsigned char *__restrict__ sm, const int *__restrict__ cf,
+                                                      const double *__restrict__ q, int *__restrict__ cnt, const int *__restrict__ brp,
+                                                      int *__restrict__ bcj, double *__restrict__ bv, double *__restrict__ dd)
+{
+   const int r = blockIdx.x * 256 + threadIdx.x;
+   if (r >= nr) return;
+   const int i = rows[r];
+   if (cf[i] != kF)
+   {
+      if (!FILL) cnt[r] = 0;
+      return;
+   }
+   double d = 0.0;
+   for (int k = rp[i]; k < rp[i + 1]; k++)
+      if (cj[k] == i) d = v[k];
+   int o = FILL ? brp[r] : 0, c = 0;
+   for (int k = rp[i]; k < rp[i + 1]; k++)
+   {
+      const int    j   = cj[k];
+      const double aij = v[k];
+      if (j == i)
+      {
+         if (FILL) { bcj[o] = i; bv[o] = 1.0; o++; }
+         c++;
+      }
+      else if (sm[k] && cf[j] == kF)
+      {
+         double ski = 0.0;
+         if (PLUSI)
+            for (int kk = rp[j]; kk < rp[j + 1]; kk++)
+               if (cj[kk] == i && sm[kk]) ski = v[kk];
+         const double den = PLUSI ? q[j] + ski : q[j];
+         if (den != 0.0)
+         {
+            const double coef = aij / den;
+            if (PLUSI) d += coef * ski;
+            if (FILL) { bcj[o] = j; bv[o] = coef; o++; }
+            c++;
+         }
+         else d += aij;
+      }
+      else if (sm[k] && cf[j] == kC) {}
+      else if (cf[j] != -3) d += aij;
+   }
+   if (FILL) dd[r] = d;
+   else cnt[r] = c;
+}
+__global__ __launch_bounds__(256) void k_mm_p_count_list(int nr, const int *__restrict__ rows, const int *__restrict__ cf, const int *__restrict__ trp,
+                                                         int *__restrict__ cnt)
+{
+   const int r = blockIdx.x * 256 + threadIdx.x;
+   if (r >= nr) return;
+   const int c = cf[rows[r]];
+   cnt[r]      = (c == kC) ? 1 : (c == kF ? trp[r + 1] - trp[r] : 0);
+}
+__global__ __launch_bounds__(256) void k_mm_p_fill_list(int nr, const int *__restrict__ rows, const int *__restrict__ cf, const int *__restrict__ cidx,
+                                                        const int *__restrict__ trp, const int *__restrict__ tcj, const double *__restrict__ tv,
+                                                        const double *__restrict__ dd, const int *__restrict__ prp, int *__restrict__ pcj,
+                                                        double *__restrict__ pv)
+{
+   const int r = blockIdx.x * 256 + threadIdx.x;
+   if (r >= nr) return;
+   const int i = rows[r];
+   int       o = prp[r];
+   if (cf[i] == kC) { pcj[o] = cidx[i]; pv[o] = 1.0; return; }
+   if (cf[i] != kF) return;
+   const double d = dd[r];
+   for (int k = trp[r]; k < trp[r + 1]; k++, o++)
+   {
+      pcj[o] = tcj[k];
+      pv[o]  = (d != 0.0) ? tv[k] / (-d) : tv[k];
+   }
+}
+// every C point of the second splitting is a C point of the first, and every other first-pass C point is an F point of the second
+__global__ __launch_bounds__(256) void k_agg_check_nested(int n, const int *__restrict__ cf1, const int *__restrict__ cf2, int *__restrict__ bad)
+{
+   const int i = blockIdx.x * 256 + threadIdx.x;
+   if (i >= n) return;
+   if ((cf2[i] == kC && cf1[i] != kC) || (cf1[i] == kC && cf2[i] != kC && cf2[i] != kF)) atomicAdd(bad, 1);
+}
+
 // ---- one-point interpolation (type 100): per F row the strong C neighbour of largest |a_ij|, the first in column order among equals
 // (FILL = false: the row's entry count).  A thread per row like the kernels above: the rows are the operator's own, a handful of entries.
 template <bool FILL>
@@ -613,6 +705,77 @@ void amg_interp_mm_extpi(const DCsr &A, const unsigned char *smask, const int *c
                                      P.val.data());
    P.reset_plan();
    amg_truncate_rows(P, pmax, trunc_factor);
+}
+
+// Second stage of the two-stage aggressive interpolation: the rows of the first-pass C points (cf1) in the mm-ext / mm-ext+i operator
+// of the final splitting cf2, columns in the numbering of the final C points -- |C1| x |C2|.  Only those rows are built: B, the
+// product B A^s_FC, the division by -d_i and the truncation run on the compacted list of C1 rows.
+void amg_interp_mm_partial(const DCsr &A, const unsigned char *smask, const int *cf1, const int *cf2, int pmax, double trunc_factor, bool plus_i,
+                           DCsr &P2)
+{
+   const int n = A.nrows, g = ceil_div(std::max(n, 1), 256);
+   DArray<int> m((size_t)n + 1), c1idx((size_t)n + 1), cidx((size_t)n + 1), nsc((size_t)n + 1), bad(1);
+   DArray<double> q((size_t)std::max(n, 1));
+   bad.zero();
+   k_agg_check_nested<<<g, 256, 0, STREAM>>>(n, cf1, cf2, bad.data());
+   k_agg_cmark<<<g, 256, 0, STREAM>>>(n, cf1, m.data());
+   exclusive_scan(n, m.data(), c1idx.data(), nullptr);
+   k_agg_cmark<<<g, 256, 0, STREAM>>>(n, cf2, m.data());
+   exclusive_scan(n, m.data(), cidx.data(), nullptr);
+   int n1 = 0, nc = 0, nbad = 0;
+   HDA_HIP(hipMemcpyAsync(&n1, c1idx.data() + n, 4, hipMemcpyDeviceToHost, STREAM));
+   HDA_HIP(hipMemcpyAsync(&nc, cidx.data() + n, 4, hipMemcpyDeviceToHost, STREAM));
+   HDA_HIP(hipMemcpyAsync(&nbad, bad.data(), 4, hipMemcpyDeviceToHost, STREAM));
+   nsc.zero();
+   k_mm_q<<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), A.val.data(), smask, cf2, q.data(), nsc.data());
+   Context::get().sync();
+   HDA_REQUIRE(nbad == 0, "two-stage aggressive interpolation: the second splitting must keep a subset of the first pass's C points and turn the others into F points");
+   const int      g1 = ceil_div(std::max(n1, 1), 256);
+   DArray<int>    rows((size_t)std::max(n1, 1)), cb((size_t)n1 + 1);
+   DArray<double> dd((size_t)std::max(n1, 1));
+   k_agg_row_list<<<g, 256, 0, STREAM>>>(n, cf1, c1idx.data(), rows.data());
+   cb.zero();
+   auto rows_count = plus_i ? k_mm_rows_list<false, true> : k_mm_rows_list<false, false>;
+   auto rows_fill  = plus_i ? k_mm_rows_list<true, true> : k_mm_rows_list<true, false>;
+   rows_count<<<g1, 256, 0, STREAM>>>(n1, rows.data(), A.rowptr.data(), A.col.data(), A.val.data(), smask, cf2, q.data(), cb.data(), nullptr, nullptr,
+                                      nullptr, nullptr);
+   DCsr B, FC, T;
+   finish_rows(n1, n, cb, B);
+   finish_rows(n, nc, nsc, FC);
+   rows_fill<<<g1, 256, 0, STREAM>>>(n1, rows.data(), A.rowptr.data(), A.col.data(), A.val.data(), smask, cf2, q.data(), nullptr, B.rowptr.data(),
+                                     B.col.data(), B.val.data(), dd.data());
+   k_mm_fc_fill<<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), A.val.data(), smask, cf2, cidx.data(), FC.rowptr.data(), FC.col.data(),
+                                      FC.val.data());
+   spgemm(B, FC, T);
+   DArray<int> pc((size_t)n1 + 1);
+   pc.zero();
+   k_mm_p_count_list<<<g1, 256, 0, STREAM>>>(n1, rows.data(), cf2, T.rowptr.data(), pc.data());
+   finish_rows(n1, nc, pc, P2);
+   k_mm_p_fill_list<<<g1, 256, 0, STREAM>>>(n1, rows.data(), cf2, cidx.data(), T.rowptr.data(), T.col.data(), T.val.data(), dd.data(), P2.rowptr.data(),
+                                           P2.col.data(), P2.val.data());
+   P2.reset_plan();
+   amg_truncate_rows(P2, pmax, trunc_factor);
+}
+
+// Two-stage mm-ext / mm-ext+i interpolation of an aggressive level (aggressive.prolongation_type 5 / 6):
+// P1 = the operator of the first-pass splitting, truncated by the P12 pair; P2 = the partial operator above, truncated by the
+// aggressive pair; P = P1 P2 on the deterministic SpGEMM (rows column-sorted), not truncated again.
+void amg_interp_agg_two_stage(const DCsr &A, const unsigned char *smask, const int *cf1, const int *cf2, bool plus_i, int p12_pmax,
+                              double p12_trunc_factor, int pmax, double trunc_factor, DCsr &P, DCsr *P1_out, DCsr *P2_out)
+{
+   DCsr P1, P2;
+   HDA_TRACE("  two-stage interpolation: first stage");
+   amg_interp_mm_extpi(A, smask, cf1, p12_pmax, p12_trunc_factor, P1, nullptr, plus_i);
+   HDA_TRACE("  two-stage interpolation: second stage (%d of %d rows)", P1.ncols, A.nrows);
+   amg_interp_mm_partial(A, smask, cf1, cf2, pmax, trunc_factor, plus_i, P2);
+   HDA_REQUIRE(P1.ncols == P2.nrows, "two-stage aggressive interpolation: the stages do not fit");
+   HDA_TRACE("  two-stage interpolation: product");
+   spgemm(P1, P2, P);
+   P.reset_plan();
+   HDA_TRACE("  two-stage mm-ext%s interpolation: P1 %d x %d (%d entries), P2 %d x %d (%d entries), P %d entries", plus_i ? "+i" : "", P1.nrows,
+             P1.ncols, P1.nnz, P2.nrows, P2.ncols, P2.nnz, P.nnz);
+   if (P1_out) *P1_out = std::move(P1);
+   if (P2_out) *P2_out = std::move(P2);
 }
 
 } // namespace hda

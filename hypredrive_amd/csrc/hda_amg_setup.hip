@@ -2192,6 +2192,21 @@ std::string amg_interp_refusal(int t)
                  "mm_extended (16), mm_extended+i (17) and one_point (100) are";
 }
 
+// interpolation of the aggressive levels (aggressive.prolongation_type; names: kAggInterp of hda_yaml.cpp)
+bool        amg_agg_interp_type_built(int t) { return t == 4 || t == 5 || t == 6; }
+const char *amg_agg_interp_name(int t)
+{
+   static const char *names[] = {nullptr, "2_stage_extended+i", "2_stage_standard", "2_stage_extended", "multipass", "mm_extended", "mm_extended+i",
+                                 "mm_extended+e"};
+   return (t >= 1 && t <= 7) ? names[t] : nullptr;
+}
+std::string amg_agg_interp_refusal(int t)
+{
+   const char *nm = amg_agg_interp_name(t);
+   return std::string("aggressive coarsening: aggressive.prolongation_type ") + (nm ? std::string(nm) + " (" + std::to_string(t) + ")" : std::to_string(t)) +
+          " is not implemented on MI355X: multipass (4), mm_extended (5) and mm_extended+i (6) are";
+}
+
 void amg_interp_extpi(const DCsr &A, const unsigned char *smask, const int *cf, int pmax,
                       double trunc_factor, DCsr &P, const int *dof, int interp_type)
 {
@@ -3091,8 +3106,8 @@ void Amg::build_hierarchy(const DCsr &A)
                "coarse relaxation must be Gaussian elimination (9), Jacobi, hybrid or two-stage Gauss-Seidel or Chebyshev");
    HDA_REQUIRE(prm.cheby_variant == 0 || (prm.relax_down != 16 && prm.relax_up != 16 && prm.relax_coarse != 16),
                "Chebyshev smoother: only variant 0 (the standard polynomial) is implemented");
-   HDA_REQUIRE(prm.agg_num_levels <= 0 || (prm.agg_interp_type == 4 && prm.num_functions <= 1),
-               "aggressive coarsening: multipass interpolation (aggressive.prolongation_type 4) on a scalar problem is what is implemented");
+   HDA_REQUIRE(prm.agg_num_levels <= 0 || amg_agg_interp_type_built(prm.agg_interp_type), amg_agg_interp_refusal(prm.agg_interp_type).c_str());
+   HDA_REQUIRE(prm.agg_num_levels <= 0 || prm.num_functions <= 1, "aggressive coarsening is implemented on a scalar problem (num_functions 1) only");
    check_air_params();
    A0 = &A;
    a0_dims[0] = A.nrows; a0_dims[1] = A.ncols; a0_dims[2] = A.nnz;
@@ -3172,11 +3187,21 @@ void Amg::build_hierarchy(const DCsr &A)
       else if (prm.coarsen_type == 6) falgout_core(Al, sm.data(), ns.data(), levels[lvl].blk_part, prm.seed, lvl + level0, cf.data());
       else pmis_core(Al, sm.data(), ns.data(), prm.seed, lvl + level0, 0, cf.data());
       const bool aggressive = lvl + level0 < prm.agg_num_levels;
+      const bool two_stage  = aggressive && prm.agg_interp_type != 4;
+      DArray<int> cf1; // the splitting after the first pass: the first stage of the two-stage interpolations is built on it
+      if (two_stage)
+      {
+         cf1.alloc((size_t)std::max(n, 1));
+         HDA_HIP(hipMemcpyAsync(cf1.data(), cf.data(), sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, STREAM));
+      }
       if (aggressive) amg_coarsen_second_pass(Al, sm.data(), prm.agg_num_paths, prm.seed, lvl + level0, cf.data());
-      HDA_TRACE("level %d: interp%s", lvl, aggressive ? " (aggressive level: multipass)" : "");
+      HDA_TRACE("level %d: interp%s", lvl, aggressive ? (std::string(" (aggressive level: ") + amg_agg_interp_name(prm.agg_interp_type) + ")").c_str() : "");
       auto t2 = tick();
       DCsr P;
-      if (aggressive)
+      if (two_stage)
+         amg_interp_agg_two_stage(Al, sm.data(), cf1.data(), cf.data(), prm.agg_interp_type == 6, prm.agg_p12_pmax, prm.agg_p12_trunc_factor,
+                                  prm.agg_pmax, prm.agg_trunc_factor, P);
+      else if (aggressive)
       {
          amg_interp_multipass(Al, sm.data(), cf.data(), P);
          amg_truncate_rows(P, prm.agg_pmax, prm.agg_trunc_factor);

@@ -119,6 +119,7 @@ extern "C" void hda_amg_default_params(hda_amg_params *p)
    p->relax_points = d.relax_points;
    p->agg_num_levels = d.agg_num_levels; p->agg_num_paths = d.agg_num_paths; p->agg_interp_type = d.agg_interp_type;
    p->agg_pmax = d.agg_pmax; p->agg_trunc_factor = d.agg_trunc_factor;
+   p->agg_p12_pmax = d.agg_p12_pmax; p->agg_p12_trunc_factor = d.agg_p12_trunc_factor;
    p->blocks = d.blocks; p->block_part = nullptr;
    p->struct_size = (int)sizeof(hda_amg_params);
 }
@@ -149,6 +150,7 @@ static AmgParams to_params(const hda_amg_params *p)
    a.relax_points = p->relax_points;
    a.agg_num_levels = p->agg_num_levels; a.agg_num_paths = p->agg_num_paths; a.agg_interp_type = p->agg_interp_type;
    a.agg_pmax = p->agg_pmax; a.agg_trunc_factor = p->agg_trunc_factor;
+   a.agg_p12_pmax = p->agg_p12_pmax; a.agg_p12_trunc_factor = p->agg_p12_trunc_factor;
    a.blocks = p->blocks;
    if (p->block_part && p->blocks > 1) a.block_part.assign(p->block_part, p->block_part + p->blocks + 1);
    return a;
@@ -627,6 +629,28 @@ extern "C" int hda_interp_multipass(hda_csr_t A, const unsigned char *smask, con
    amg_interp_multipass(m, sm.data(), dcf.data(), h->m);
    Context::get().sync();
    *P = h.release();
+   HDA_CATCH
+}
+
+// two-stage mm-ext (plus_i 0) / mm-ext+i (1) interpolation of an aggressive level; P1 / P2 / P: the stages and the product (any may be NULL)
+extern "C" int hda_interp_agg_two_stage(hda_csr_t A, const unsigned char *smask, const int *cf1, const int *cf2, int plus_i, int p12_pmax,
+                                        double p12_trunc_factor, int pmax, double trunc_factor, hda_csr_t *P1, hda_csr_t *P2, hda_csr_t *P)
+{
+   HDA_TRY
+   HDA_REQUIRE(A && smask && cf1 && cf2, "hda_interp_agg_two_stage: A, smask, cf1 and cf2 are required");
+   const DCsr           &m = A->get();
+   DArray<unsigned char> sm;
+   DArray<int>           d1, d2;
+   sm.upload(smask, (size_t)std::max(m.nnz, 1));
+   d1.upload(cf1, (size_t)std::max(m.nrows, 1));
+   d2.upload(cf2, (size_t)std::max(m.nrows, 1));
+   auto h1 = std::make_unique<hda_csr_s>(), h2 = std::make_unique<hda_csr_s>(), h = std::make_unique<hda_csr_s>();
+   if (!P1 && !P) amg_interp_mm_partial(m, sm.data(), d1.data(), d2.data(), pmax, trunc_factor, plus_i != 0, h2->m); // the second stage alone
+   else amg_interp_agg_two_stage(m, sm.data(), d1.data(), d2.data(), plus_i != 0, p12_pmax, p12_trunc_factor, pmax, trunc_factor, h->m, &h1->m, &h2->m);
+   Context::get().sync();
+   if (P1) *P1 = h1.release();
+   if (P2) *P2 = h2.release();
+   if (P) *P = h.release();
    HDA_CATCH
 }
 

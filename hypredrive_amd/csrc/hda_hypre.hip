@@ -1205,8 +1205,9 @@ HY_SETTER(HYPRE_BoomerAMGSetILUDroptol, HYPRE_Real, (void)v)   // threshold vari
 HY_SETTER(HYPRE_BoomerAMGSetILUMaxRowNnz, HYPRE_Int, (void)v)  // threshold variants only
 HY_SETTER(HYPRE_BoomerAMGSetILUMaxIter, HYPRE_Int, s->ap.smooth_num_sweeps = v) // amg.c:921 passes smoother.num_sweeps
 HY_SETTER(HYPRE_BoomerAMGSetSmoothNumLevels, HYPRE_Int, s->smooth_num_levels = v)
-// aggressive coarsening (reference src/internal/amg.c:938-944): levels, paths and the multipass interpolation are built
-// (hda_amg_agg.hip); a truncation of the aggressive levels' interpolation or a two-stage (P12) type is refused at Setup
+// aggressive coarsening (reference src/internal/amg.c:938-944): levels, paths, the multipass interpolation (4) and the two-stage
+// mm_extended (5) / mm_extended+i (6) interpolations with their P12 truncation are built (hda_amg_agg.hip); the other two-stage types
+// (1, 2, 3, 7) are refused by name at Setup
 HY_SETTER(HYPRE_BoomerAMGSetAggNumLevels, HYPRE_Int, s->agg_num_levels = v)
 HY_SETTER(HYPRE_BoomerAMGSetAggInterpType, HYPRE_Int, s->ap.agg_interp_type = v)
 HY_SETTER(HYPRE_BoomerAMGSetAggTruncFactor, HYPRE_Real, s->agg_trunc[0] = v)
@@ -1279,10 +1280,12 @@ extern "C" HYPRE_Int HYPRE_BoomerAMGSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, 
    s->ap.agg_num_levels = std::max(s->agg_num_levels, 0);
    if (s->ap.agg_num_levels > 0)
    {
-      HDA_REQUIRE(s->ap.agg_interp_type == 4, "aggressive coarsening: only multipass interpolation (aggressive.prolongation_type 4 / multipass) is implemented on MI355X");
+      HDA_REQUIRE(amg_agg_interp_type_built(s->ap.agg_interp_type), amg_agg_interp_refusal(s->ap.agg_interp_type).c_str());
       s->ap.agg_trunc_factor = s->agg_trunc[0];
       s->ap.agg_pmax         = (int)s->agg_trunc[2];
-      // (P12_* concern the two-stage interpolation types only, which are refused above: accepted and unused, as in hypre with type 4)
+      // P12_*: the first stage of the two-stage types (5 / 6); accepted and unused with multipass, as in hypre
+      s->ap.agg_p12_trunc_factor = s->agg_trunc[1];
+      s->ap.agg_p12_pmax         = (int)s->agg_trunc[3];
    }
    if (s->smooth_num_levels > 0)
    {

@@ -52,8 +52,12 @@ typedef struct {
    int      restrict_type;
    double   restrict_strong_th, restrict_filter_th;
    int      relax_points;
+   /* aggressive.P12_max_elements / P12_trunc_factor: truncation of the first stage of the two-stage interpolations (agg_interp_type 5 / 6) */
+   int      agg_p12_pmax;
+   double   agg_p12_trunc_factor;
    /* AMGagg_args (src/internal/amg.c:160-173, forwarded at :938-944): aggressive coarsening on the first agg_num_levels levels
-    * (second PMIS pass over the graph of >= agg_num_paths paths of length <= 2), multipass interpolation (agg_interp_type 4) there */
+    * (second PMIS pass over the graph of >= agg_num_paths paths of length <= 2); agg_interp_type there: 4 multipass, 5 two-stage
+    * mm_extended, 6 two-stage mm_extended+i */
    int      agg_num_levels, agg_num_paths, agg_interp_type;
    int      agg_pmax;         /* aggressive.max_nnz_row (0: no limit) */
    double   agg_trunc_factor; /* aggressive.trunc_factor */
@@ -164,6 +168,13 @@ int hda_coarsen_second_pass(hda_csr_t A, const unsigned char *smask, int num_pat
 int hda_interp_multipass(hda_csr_t A, const unsigned char *smask, const int *cf, hda_csr_t *P);
 /* hypre_BoomerAMGInterpTruncation on the finished rows of P, in place (HYPRE_BoomerAMGSetAggPMaxElmts / SetAggTruncFactor) */
 int hda_truncate_rows(hda_csr_t P, int pmax, double trunc_factor);
+/* two-stage interpolation of an aggressive level (HYPRE_BoomerAMGSetAggInterpType 5 mm_extended: plus_i 0; 6 mm_extended+i: plus_i 1):
+ * cf1 the splitting after the first coarsening pass, cf2 after hda_coarsen_second_pass.  P1 (n x |C1|): the mm operator of cf1,
+ * truncated by p12_pmax / p12_trunc_factor (SetAggP12MaxElmts / SetAggP12TruncFactor); P2 (|C1| x |C2|): the C1 rows of the mm
+ * operator of cf2, truncated by pmax / trunc_factor; P = P1 P2.  Any of the three outputs may be NULL; with P2 alone asked for, only
+ * the second stage is built */
+int hda_interp_agg_two_stage(hda_csr_t A, const unsigned char *smask, const int *cf1, const int *cf2, int plus_i, int p12_pmax,
+                             double p12_trunc_factor, int pmax, double trunc_factor, hda_csr_t *P1, hda_csr_t *P2, hda_csr_t *P);
 int hda_transpose(hda_csr_t A, hda_csr_t *T);
 int hda_spgemm(hda_csr_t X, hda_csr_t Y, hda_csr_t *C);
 
