@@ -94,6 +94,7 @@ SYMBOLS = [
     "hda_csr_form", "hda_spmv_mode", "hda_air_restriction",
     "hda_cljp", "hda_rs_blocks", "hda_falgout_blocks", "hda_measure_rnd",
     "hda_schwarz_create", "hda_schwarz_domains", "hda_schwarz_info", "hda_precond_time",
+    "hda_spgemm_last_route", "hda_sort_rows_last_route",
 ]
 
 
@@ -179,6 +180,8 @@ def load():
     L.hda_interp_agg_two_stage.argtypes = [vp, P(C.c_ubyte), ip, ip, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, P(vp), P(vp), P(vp)]
     L.hda_transpose.argtypes = [vp, P(vp)]
     L.hda_spgemm.argtypes = [vp, vp, P(vp)]
+    L.hda_spgemm_last_route.argtypes = [P(C.c_int64)]
+    L.hda_sort_rows_last_route.argtypes = [P(C.c_int64)]
     L.hda_amg_create.argtypes = [P(AmgParams), vp, P(vp)]
     L.hda_amg_destroy.argtypes = [vp]
     L.hda_mgr_create.argtypes = [vp, ip, C.c_int, P(MgrLevelParams), P(AmgParams), C.c_int, P(vp)]
@@ -503,6 +506,28 @@ class Csr:
         out = C.c_void_p()
         _check(load().hda_spgemm(self.h, Y.h, C.byref(out)))
         return Csr(out)
+
+
+SPGEMM_PATHS = ("none", "esc", "hash")
+SPGEMM_WHY_HASH = ("none", "empty input", "row longer than 4096 products", "scratch budget", "row-field overflow")
+SORT_ROUTES = ("none", "insertion", "wave", "segmented")
+
+
+def spgemm_last_route():
+    """hda_spgemm_last_route: the route of this thread's last sparse product (Csr.matmul, the second product of Csr.rap, the last of
+    a setup).  capacity, threads and nchunks are 0 on the hash path, batches 0 on the LDS path."""
+    o = (C.c_int64 * 8)()
+    _check(load().hda_spgemm_last_route(o))
+    return {"path": SPGEMM_PATHS[o[0]], "why_hash": SPGEMM_WHY_HASH[o[1]], "capacity": o[2], "threads": o[3],
+            "nchunks": o[4], "maxnp": o[5], "total": o[6], "batches": o[7]}
+
+
+def sort_rows_last_route():
+    """hda_sort_rows_last_route: "none", "insertion", "wave" or "segmented" -- the last row sort of this thread (Csr.from_arrays,
+    Csr.transpose)"""
+    r = C.c_int64()
+    _check(load().hda_sort_rows_last_route(C.byref(r)))
+    return SORT_ROUTES[r.value]
 
 
 def lap7(nx, ny, nz, c=(1.0, 1.0, 1.0), want_rhs=True):

@@ -2491,6 +2491,7 @@ static void spgemm_hash(const DCsr &X, const DCsr &Y, DCsr &C)
    C.nrows     = n;
    C.ncols     = Y.ncols;
    C.rowptr.alloc((size_t)n + 1);
+   setup_route().batches = 0;
    if (n == 0)
    {
       C.rowptr.zero();
@@ -2529,6 +2530,7 @@ static void spgemm_hash(const DCsr &X, const DCsr &Y, DCsr &C)
    else
       bstart.push_back(n);
    const int nb = (int)bstart.size() - 1;
+   setup_route().batches = nb;
    long long maxslots = 0;
    if (nb == 1) maxslots = H;
    else
@@ -2819,7 +2821,16 @@ void spgemm(const DCsr &X, const DCsr &Y, DCsr &C)
 {
    HDA_REQUIRE(X.ncols <= Y.nrows || X.nnz == 0, "spgemm: inner dimensions");
    const int n = X.nrows;
-   if (n == 0 || X.nnz == 0 || use_hash_spgemm()) return spgemm_hash(X, Y, C);
+   SetupRoute &route = setup_route();
+   const int   sorted = route.sort;
+   route      = SetupRoute();
+   route.sort = sorted;
+   auto hash  = [&](int why) {
+      route.path = 2;
+      route.why  = why;
+      return spgemm_hash(X, Y, C);
+   };
+   if (n == 0 || X.nnz == 0 || use_hash_spgemm()) return hash(1);
    DArray<int>       elen((size_t)X.nnz + 1), mx(1);
    DArray<long long> eoff((size_t)X.nnz + 1);
    k_entry_len<<<std::min(ceil_div(X.nnz, 256), 1 << 16), 256, 0, STREAM>>>(X.nnz, X.col.data(), Y.rowptr.data(), elen.data());
@@ -2844,7 +2855,9 @@ void spgemm(const DCsr &X, const DCsr &Y, DCsr &C)
       if (hipMemGetInfo(&freeb, &totalb) != hipSuccess) return 3LL << 30;
       return (long long)(0.3 * (double)totalb / 12.0);
    }(); // products
-   if (maxnp > 4096 || total > scratch_cap) return spgemm_hash(X, Y, C); // outside the LDS path
+   route.maxnp = maxnp;
+   route.total = total;
+   if (maxnp > 4096 || total > scratch_cap) return hash(maxnp > 4096 ? 2 : 3); // outside the LDS path
    const int nchunks = (int)std::max<long long>(1, (total + T - 1) / T);
    DArray<int>       chunk_row((size_t)nchunks + 1), cnt((size_t)n + 1);
    DArray<long long> rowstart((size_t)n + 1), chunkbase((size_t)n + 1);
@@ -2882,11 +2895,15 @@ void spgemm(const DCsr &X, const DCsr &Y, DCsr &C)
    HDA_HIP(hipMemcpyAsync(&C.nnz, C.rowptr.data() + n, 4, hipMemcpyDeviceToHost, STREAM));
    HDA_HIP(hipMemcpyAsync(&overflow, mx.data(), 4, hipMemcpyDeviceToHost, STREAM));
    Context::get().sync();
-   if (overflow) return spgemm_hash(X, Y, C); // a chunk spanned 2^19 rows or more (long runs of empty rows)
+   if (overflow) return hash(4); // a chunk spanned 2^19 rows or more (long runs of empty rows)
    C.col.alloc((size_t)std::max(C.nnz, 1));
    C.val.alloc((size_t)std::max(C.nnz, 1));
    k_esc_compact<<<std::min(ceil_div((long long)n * 8, 256), 1 << 16), 256, 0, STREAM>>>(n, C.rowptr.data(), rowstart.data(), scol.data(),
                                                                                   sval.data(), C.col.data(), C.val.data());
+   route.path    = 1;
+   route.cap     = cap;
+   route.nt      = nt;
+   route.nchunks = nchunks;
    HDA_TRACE("  spgemm(esc): nnz=%d", C.nnz);
 }
 

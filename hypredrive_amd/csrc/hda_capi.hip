@@ -682,6 +682,24 @@ extern "C" int hda_spgemm(hda_csr_t X, hda_csr_t Y, hda_csr_t *C)
    HDA_CATCH
 }
 
+extern "C" int hda_spgemm_last_route(int64_t out[8])
+{
+   HDA_TRY
+   HDA_REQUIRE(out, "hda_spgemm_last_route: out is required");
+   const SetupRoute &r = setup_route();
+   out[0] = r.path; out[1] = r.why; out[2] = r.cap; out[3] = r.nt;
+   out[4] = r.nchunks; out[5] = r.maxnp; out[6] = r.total; out[7] = r.batches;
+   HDA_CATCH
+}
+
+extern "C" int hda_sort_rows_last_route(int64_t *route)
+{
+   HDA_TRY
+   HDA_REQUIRE(route, "hda_sort_rows_last_route: route is required");
+   *route = setup_route().sort;
+   HDA_CATCH
+}
+
 extern "C" int hda_rap(hda_csr_t A, hda_csr_t P, hda_csr_t *Ac)
 {
    HDA_TRY

@@ -100,6 +100,16 @@ void sort_rows(DCsr &A);                                    // column-sort every
 void sort_rows_segmented(DCsr &A);                          // the same by one segmented radix sort (any row length)
 void transpose(const DCsr &A, DCsr &T);                     // rows of T sorted
 void transpose_pattern_unsorted(const DCsr &A, DArray<int> &trp, DArray<int> &tcj); // pattern of A^T, rows unordered
+// ---- route read-back (test entries hda_spgemm_last_route / hda_sort_rows_last_route): what the last spgemm() and the last sort_rows()
+// of this rank thread decided from the content of their inputs.  Host values only, written on the setup path
+struct SetupRoute {
+   // path: 0 none yet, 1 expand/sort/compress in LDS, 2 hash.  why (hash only): 1 empty input, 2 a row of more than 4096 products,
+   // 3 product scratch beyond the budget, 4 a chunk of 2^19 rows or more (row field of the sort key)
+   int       path = 0, why = 0, cap = 0, nt = 0, nchunks = 0, maxnp = 0, batches = 0;
+   long long total = 0;
+   int       sort = 0; // last sort_rows: 0 none (no rows), 1 per-thread insertion, 2 wavefront network, 3 segmented radix sort
+};
+SetupRoute &setup_route();
 // 7-pt Laplacian generator on device (examples/src/C_laplacian/laplacian.c:719-921),
 // rows [ilower, iupper] of the block-partitioned numbering; cols are GLOBAL ids (int64).
 void lap7_generate(const int n[3], const int P[3], const int pc[3], const double c[3],

@@ -3064,11 +3064,15 @@ void sort_rows_segmented(DCsr &C)
    C.col = std::move(k2);
    C.val = std::move(v2);
 }
+SetupRoute &setup_route() { return RankState<SetupRoute>::get(); }
 void sort_rows(DCsr &A)
 {
+   int &route = setup_route().sort;
+   route      = 0;
    if (!A.nrows) return;
    // long rows (the operators of coarse levels: 50-100 entries and more): the wave kernel below sorts rows of more than 64 entries by
    // insertion on ONE lane -- 50 ms per transpose of a 198 k-row level with 80-entry rows in the round-5 series-B trace
+   route = A.avg_row() > 40.0 ? 3 : A.avg_row() > 12.0 ? 2 : 1;
    if (A.avg_row() > 40.0) return sort_rows_segmented(A);
    if (A.avg_row() > 12.0)
       k_sort_rows_wave<<<std::min(ceil_div((long long)A.nrows * 64, 256), 1 << 16), 256, 0, STREAM>>>(A.nrows, A.rowptr.data(), A.col.data(),

@@ -177,6 +177,15 @@ int hda_interp_agg_two_stage(hda_csr_t A, const unsigned char *smask, const int 
                              double p12_trunc_factor, int pmax, double trunc_factor, hda_csr_t *P1, hda_csr_t *P2, hda_csr_t *P);
 int hda_transpose(hda_csr_t A, hda_csr_t *T);
 int hda_spgemm(hda_csr_t X, hda_csr_t Y, hda_csr_t *C);
+/* test entries: which route the last sparse product (hda_spgemm, the two of hda_rap, those of a setup) and the last row sort
+ * (hda_csr_create, hda_transpose) of the calling thread took -- both choose their kernel from the content of their inputs.
+ * out: [0] path (0 none yet, 1 expand/sort/compress in LDS, 2 hash), [1] why hash (0 not, 1 empty input, 2 a row of more than 4096
+ * products, 3 product scratch beyond the budget, 4 a chunk of 2^19 rows or more), [2] chunk capacity in products and [3] workgroup
+ * size of the LDS kernel, [4] chunks, [5] most products of a row, [6] products in all, [7] row batches of the hash product
+ * ([2]..[4] are 0 on the hash path, [5] and [6] 0 for an empty input).  route: 0 none (no rows), 1 per-thread insertion,
+ * 2 wavefront network (rows of more than 64 entries by insertion on one lane), 3 segmented radix sort */
+int hda_spgemm_last_route(int64_t out[8]);
+int hda_sort_rows_last_route(int64_t *route);
 
 /* ---- hierarchy + V-cycle ----------------------------------------------------------- */
 /* HYPRE_BoomerAMGCreate/Setup (src/internal/precon.c:107) */

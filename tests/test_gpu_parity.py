@@ -966,24 +966,16 @@ def test_edge_cases(orc, hd, pins):
 
 
 def test_spgemm_batched_equals_unbatched(orc, hd, tmp_path):
-    """Force the row-batched SpGEMM path with a tiny hash budget (env read once per process,
-    so run in a subprocess)."""
-    import os
-    import subprocess
-    import sys
-    code = (
-        "import sys, numpy as np, hypredrive_amd as h\n"
-        "A = h.lap7(14,14,14); sm = A.strength(); cf = A.pmis(sm); P = A.interp_extpi(sm, cf)\n"
-        "rp, cj, v = A.rap(P).download(); np.savez(sys.argv[1], rp=rp, cj=cj, v=v)\n")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for slots in ("d", "4096"):
-        env = dict(os.environ, PYTHONPATH=root)
-        if slots != "d":
-            env["HDA_SPGEMM_SLOTS"] = slots
-        else:
-            env.pop("HDA_SPGEMM_SLOTS", None)
-        subprocess.check_call([sys.executable, "-c", code, str(tmp_path / f"rap_{slots}.npz")], env=env, cwd=root)
-    a, b = np.load(tmp_path / "rap_d.npz"), np.load(tmp_path / "rap_4096.npz")
+    """Force the row-batched hash product with a tiny slot budget (env read once per process, so run in a subprocess).  The input has
+    a row of 65 x 64 products, beyond the LDS kernel, so both runs really enter the hash product: the read-back route says so, one
+    batch by default and several with the budget (tests/spgemm_reference.py; every budget and the reference: tests/test_gpu_spgemm.py)."""
+    import spgemm_reference as R
+    routes, arrays = {}, {}
+    for slots in (None, 4096):
+        routes[slots], arrays[slots] = R.batched_child(slots, tmp_path / f"c_{slots}.npz")
+        assert routes[slots]["path"] == "hash" and routes[slots]["why_hash"] == "row longer than 4096 products", routes[slots]
+    assert routes[None]["batches"] == 1 and routes[4096]["batches"] > 1
+    a, b = arrays[None], arrays[4096]
     for k in ("rp", "cj", "v"):
         assert np.array_equal(a[k], b[k])
 
