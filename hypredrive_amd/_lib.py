@@ -84,7 +84,7 @@ SYMBOLS = [
     "hda_csr_dims", "hda_csr_download", "hda_lap7_create", "hda_spmv", "hda_relax", "hda_dot",
     "hda_l1_norms", "hda_strength", "hda_pmis", "hda_interp_extpi", "hda_interp_direct", "hda_rap", "hda_transpose",
     "hda_spgemm", "hda_amg_create", "hda_amg_destroy", "hda_amg_num_levels",
-    "hda_last_precond_calls", "hda_amg_create_dof", "hda_format_bytes", "hda_probe_spmv", "hda_probe_read", "hda_amg_level_matrix", "hda_amg_level_cf", "hda_amg_complexities", "hda_amg_vcycle_bytes",
+    "hda_last_precond_calls", "hda_amg_create_dof", "hda_format_bytes", "hda_probe_spmv", "hda_probe_read", "hda_amg_level_matrix", "hda_amg_fold_sweep", "hda_amg_level_cf", "hda_amg_complexities", "hda_amg_vcycle_bytes",
     "hda_amg_vcycle", "hda_pcg", "hda_gmres", "hda_time_kernel", "hda_solve_device",
     "hda_pcg_iteration_bytes", "hda_memory_stats", "hda_memory_cached", "hda_memory_driver_stats", "hda_memory_trim", "hda_comm_selftest", "hda_check_row_total", "hda_ilu_create", "hda_ilu_create_blocks", "hda_ilu_blocks", "hda_ilu_factors", "hda_fgmres", "hda_bicgstab", "hda_mgr_create", "hda_mgr_matrix", "hda_mgr_blk_inverses",
     "hda_probe_add", "hda_probe_read_id", "hda_borrow_hypredrv", "hda_comm_stats", "hda_comm_name", "hda_comm_size", "hda_halo_plan_host",
@@ -200,6 +200,7 @@ def load():
     L.hda_amg_num_levels.argtypes = [vp]
     L.hda_amg_level_matrix.argtypes = [vp, C.c_int, C.c_int, P(vp)]
     L.hda_amg_level_cf.argtypes = [vp, C.c_int, ip]
+    L.hda_amg_fold_sweep.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp]
     L.hda_amg_complexities.argtypes = [vp, dp, dp]
     L.hda_amg_vcycle_bytes.argtypes = [vp]
     L.hda_amg_vcycle_bytes.restype = C.c_double
@@ -568,6 +569,15 @@ class Amg:
         out = C.c_void_p()
         _check(load().hda_amg_level_matrix(self.h, level, which, C.byref(out)))
         return Csr(out, owned=False, keep=self)
+
+    def fold_sweep(self, level, dinv, t, e, u):
+        """The folded up-leg sweep of a folded level as the cycle launches it: (u + dinv * t) + Pt e, Pt = level_matrix(level, 3)."""
+        dinv, t, e, u = (np.ascontiguousarray(v, dtype=np.float64) for v in (dinv, t, e, u))
+        M = self.level_matrix(level, 3)
+        assert dinv.size == t.size == u.size == M.nrows and e.size == M.ncols
+        out = np.zeros(M.nrows)
+        _check(load().hda_amg_fold_sweep(self.h, level, _dp(dinv), _dp(t), _dp(e), _dp(u), _dp(out)))
+        return out
 
     def ilu_factors(self, level):
         """Factors of the complex smoother (amg.smoother.type ilu) of a level."""

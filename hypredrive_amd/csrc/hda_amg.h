@@ -253,6 +253,11 @@ FirstSweepFusion &first_sweep_fusion();
 
 struct AmgLevel {
    DCsr           A, P, R;
+   // folded up leg (one-rank hierarchies, levels 1 .. L-2): until build_smoother_data has decided, A_l P_l as the
+   // Galerkin product left it; on a folded level P~ = P - diag(dinv_up) (A_l P_l), which the cycle streams once in place of the
+   // prolongation and the first post-smoothing sweep over A_l; empty on every other level
+   DCsr           Pt;
+   bool           folded = false;
    // row partitions: the P rows of this rank's GHOST fine points (the ghost slots of hA, in their order; columns as P's), so that
    // the prolongation updates the ghost copies of the iterate too and the first post-smoothing sweep needs no exchange
    DCsr           Pg;
@@ -292,7 +297,8 @@ class Amg {
    std::vector<int> dof_func0;
    long long        dof_row_offset = 0;
    // hypre_BoomerAMGSetup (src/internal/precon.c:107): A is borrowed for level 0.
-   void setup(const DCsr &A);
+   // fold_up = false: no level's up leg is folded (the replicated tail of a partitioned hierarchy)
+   void setup(const DCsr &A, bool fold_up = true);
    // Row-partitioned variant: Aloc is this rank's block ([owned | ghost] columns, ghosts =
    // ghost_gids ascending), hA0 its halo plan, part0 the row starts of all ranks.  Round-1
    // scheme: the operator is gathered and the hierarchy is built redundantly on every rank
@@ -335,6 +341,7 @@ class Amg {
    double        grid_complexity() const;
    // algorithmic HBM bytes of one V-cycle (SURVEY 8(d) formulas on the built hierarchy)
    double        vcycle_bytes(bool format = false) const; // format: bytes the kernels read (coded operators), else the CSR figure
+   bool          level_folded(int l) const { return l >= 0 && l < num_levels() && levels[(size_t)l].folded; }
    AmgParams     prm;
    int           blocks_used = 1;      // row blocks the setup worked with (AmgParams::blocks resolved)
    const std::vector<int> &level_blocks(int l) const { return levels[(size_t)l].blk_part; }
@@ -348,8 +355,9 @@ class Amg {
    const double *sweep_dinv(int l, int dir, int s);     // divisors of that sweep on level l (masked for F / C sweeps)
    void          check_air_params() const;              // restriction_type / relaxation points: refusal by name of what is not built
    bool          needs_cf_in_cycle() const;             // some sweep relaxes F or C points only
-   void build_hierarchy(const DCsr &A);
+   void build_hierarchy(const DCsr &A, bool keep_ap = false); // keep_ap: levels >= 1 keep A_l P_l in AmgLevel::Pt (fold_level)
    void build_smoother_data(int l); // divisors (and Gauss-Seidel level sets) of level l on the matrix the cycle uses
+   bool fold_level(int l);          // P~ of level l from the level's A P and its new up divisors, or the refusal of the fold (AmgLevel::Pt freed)
    void build_cheby(int l);         // eigenvalue estimate and polynomial of the Chebyshev smoother
    void cheby_sweep(int l, const double *b, double *u, bool zero_guess, bool ghosts_fresh = false);
    bool ghosts_fresh_ = false; // cycle -> relax: the next sweep's input has fresh ghost copies (AmgLevel::Pg)
@@ -555,7 +563,8 @@ std::string amg_interp_refusal(int t);
 // hypre_ParCSRMatMat-style product C = X*Y, deterministic accumulation order, rows sorted.
 void spgemm(const DCsr &X, const DCsr &Y, DCsr &C);
 // hypre_BoomerAMGBuildCoarseOperator: Ac = R*(A*P) with R = P^T
-void amg_rap(const DCsr &A, const DCsr &P, const DCsr &R, DCsr &Ac);
+// AP_out: where the intermediate product A P is left instead of being discarded
+void amg_rap(const DCsr &A, const DCsr &P, const DCsr &R, DCsr &Ac, DCsr *AP_out = nullptr);
 // approximate ideal restriction (hda_air.hip) for the splitting cf (device; > 0 C, < 0 F): R is nc x n, rows
 // column-sorted.  stats: rows that fell back to injection, the largest neighbourhood, rows solved by the small / mid / large tier
 void air_restriction(const DCsr &A, const int *cf, int distance, double strong_th, double filter_th, DCsr &R, long long stats[5]);

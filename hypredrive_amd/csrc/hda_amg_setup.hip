@@ -2907,11 +2907,12 @@ void spgemm(const DCsr &X, const DCsr &Y, DCsr &C)
    HDA_TRACE("  spgemm(esc): nnz=%d", C.nnz);
 }
 
-void amg_rap(const DCsr &A, const DCsr &P, const DCsr &R, DCsr &Ac)
+void amg_rap(const DCsr &A, const DCsr &P, const DCsr &R, DCsr &Ac, DCsr *AP_out)
 {
    DCsr AP;
    spgemm(A, P, AP);
    spgemm(R, AP, Ac);
+   if (AP_out) *AP_out = std::move(AP);
 }
 
 // --------------------------------------------------------------- hierarchy
@@ -3040,8 +3041,81 @@ void Amg::build_smoother_data(int l)
    // launch plans of the operators the cycle applies (chunk plans, stencil coding attempt):
    // part of the setup, not of the first solve
    spmv_prepare(Al);
-   if (!last) { spmv_prepare(lv.P); spmv_prepare(lv.R); }
+   // folded up leg: made here, where the up divisors are, so that P~ never outlives the divisors inside it
+   const bool folded = !last && fold_level(l);
+   if (!last)
+   {
+      if (!folded) spmv_prepare(lv.P); // (a folded level applies P only with HDA_FOLD_UP=0: its plan waits for that)
+      spmv_prepare(lv.R);
+   }
    if (!last && lv.pg_ready && lv.Pg.nrows) spmv_prepare(lv.Pg);
+}
+
+// ---- folded up leg ---------------------------------------------------------------------------------------
+// The down leg of level l leaves t = f - A u; the up leg computes w = u + P e and then u' = w + D^-1 (f - A w).  Since
+// f - A w = t - (A P) e:   u' = (u + D^-1 t) + P~ e,   P~ = P - D^-1 (A P)   -- one pass over P~ in place of one over P and one over A.
+// Row r of P~ in the storage of row r of A P.  P's row is looked up inside it by column (after the solve-phase renumbering neither
+// row is column-sorted); a_rr != 0 puts P's pattern inside A P's -- rows where an entry of P finds no place are counted in *miss.
+__global__ __launch_bounds__(256) void k_fold_rows(int n, const int *__restrict__ prp, const int *__restrict__ pcj, const double *__restrict__ pv,
+                                                   const double *__restrict__ dinv, const int *__restrict__ arp, const int *__restrict__ acj,
+                                                   double *__restrict__ av, int *miss)
+{
+   constexpr int LPR  = 8;
+   const int     lane = threadIdx.x & (LPR - 1);
+   for (long r = ((long)blockIdx.x * 256 + threadIdx.x) / LPR; r < n; r += (long)gridDim.x * 256 / LPR)
+   {
+      const int    ps = prp[r], pe = prp[r + 1], s = arp[r], e = arp[r + 1];
+      const double d  = dinv[r];
+      int          found = 0;
+      for (int k = s + lane; k < e; k += LPR)
+      {
+         const int c = acj[k];
+         double    p = 0.0;
+         for (int j = ps; j < pe; j++)
+            if (pcj[j] == c) { p = pv[j]; found++; }
+         av[k] = p - d * av[k];
+      }
+      for (int o = LPR / 2; o > 0; o >>= 1) found += __shfl_xor(found, o);
+      if (lane == 0 && found != pe - ps) atomicAdd(miss, 1);
+   }
+}
+
+bool Amg::fold_level(int l)
+{
+   AmgLevel   &lv  = levels[(size_t)l];
+   const DCsr &Al  = level_A(l);
+   // (every setup path builds the smoother data of a level once, on a fresh hierarchy: Pt holds A P here, never an earlier P~)
+   HDA_REQUIRE(!lv.folded, "folded up leg: the divisors of a folded level are rebuilt by a new setup only");
+   auto refuse = [&](const char *why) {
+      HDA_TRACE("level %d: up leg not folded (%s)", l, why);
+      lv.Pt = DCsr();
+      return false;
+   };
+   if (lv.Pt.nrows == 0) return false; // no A P kept: level 0, the coarsest level, row partitions, a replicated tail
+   if (dist || l < 1 || l >= num_levels() - 1) return refuse("level");
+   if (!is_jacobi_type(prm.relax_up) || prm.sweeps_up < 1) return refuse("no Jacobi sweep opens the up leg");
+   if (lv.ilu) return refuse("complex smoother");
+   if (sweep_points(1, 0) != 0) return refuse("F / C relaxation");
+   DCsr &M = lv.Pt;
+   HDA_REQUIRE(M.nrows == Al.nrows && M.ncols == lv.P.ncols, "folded up leg: A P does not have the shape of P");
+   DArray<int> miss(1);
+   miss.zero();
+   const int n = M.nrows;
+   k_fold_rows<<<std::min(ceil_div((long long)n * 8, 256), 1 << 16), 256, 0, STREAM>>>(n, lv.P.rowptr.data(), lv.P.col.data(), lv.P.val.data(),
+                                                                                        sweep_dinv(l, 1, 0), M.rowptr.data(), M.col.data(),
+                                                                                        M.val.data(), miss.data());
+   int m = 0;
+   miss.download(&m, 1);
+   if (m) return refuse("an entry of P outside the pattern of A P");
+   M.reset_plan();
+   spmv_prepare(M);
+   if (!spmv_foldable(M)) return refuse("storage form of P~ without a folded kernel");
+   // it pays when P~ streams fewer bytes than A_l and P_l together (P_l's own plan is only built when A_l alone does not settle it)
+   const double bm = matrix_stream_bytes(M, true), ba = matrix_stream_bytes(Al, true);
+   if (!(bm < ba) && !(bm < ba + matrix_stream_bytes(lv.P, true))) return refuse("P~ streams no fewer bytes than A and P");
+   lv.folded = true;
+   HDA_TRACE("level %d: up leg folded, nnz(P~) %d = %.3f nnz(A), %.1f of %.1f MB", l, M.nnz, (double)M.nnz / std::max(Al.nnz, 1), bm / 1e6, ba / 1e6);
+   return true;
 }
 
 __global__ __launch_bounds__(256) void k_cmark(int n, const int *__restrict__ cf, int *__restrict__ m);
@@ -3104,7 +3178,7 @@ const double *Amg::sweep_dinv(int l, int dir, int s)
    return (dir == 0 || same_divisors(prm.relax_up, prm.relax_down)) ? lv.dinv_down.data() : lv.dinv_up.data();
 }
 
-void Amg::build_hierarchy(const DCsr &A)
+void Amg::build_hierarchy(const DCsr &A, bool keep_ap)
 {
    HDA_REQUIRE(amg_coarsen_type_built(prm.coarsen_type), amg_coarsen_refusal(prm.coarsen_type).c_str());
    const bool block_coarsening = prm.coarsen_type == 10 || prm.coarsen_type == 1 || prm.coarsen_type == 6; // a Ruge pass per row block
@@ -3266,7 +3340,8 @@ void Amg::build_hierarchy(const DCsr &A)
       auto t4 = tick();
       levels.emplace_back();
       levels[lvl + 1].blk_part = std::move(next_part);
-      amg_rap(Al, levels[lvl].P, levels[lvl].R, levels[lvl + 1].A);
+      // (levels >= 1 of a one-rank hierarchy keep A P: the folded up leg is made of it, fold_level)
+      amg_rap(Al, levels[lvl].P, levels[lvl].R, levels[lvl + 1].A, (keep_ap && lvl >= 1) ? &levels[lvl].Pt : nullptr);
       auto t5 = tick();
       if (verbose)
          fprintf(stderr, "[hda] setup level %d: n=%d nnz=%d -> nc=%d nnzP=%d nnzAc=%d | strength %.2f pmis %.2f interp %.2f transpose %.2f rap %.2f ms\n",
@@ -3298,11 +3373,11 @@ void Amg::build_hierarchy(const DCsr &A)
    coarse_nloc = coarse_n;
 }
 
-void Amg::setup(const DCsr &A)
+void Amg::setup(const DCsr &A, bool fold_up)
 {
    dist = false;
    hA0  = nullptr;
-   build_hierarchy(A);
+   build_hierarchy(A, fold_up); // (a hierarchy that may fold its up legs keeps A_l P_l of the levels >= 1)
    reorder_levels(); // solve-phase numbering of the big coarse levels (the setup above stays in natural order)
    const int L = (int)levels.size();
    for (int l = 0; l < L; l++)
@@ -3539,11 +3614,14 @@ double Amg::vcycle_bytes(bool format) const
       {
          s += 24.0 * n;                                            // zero-guess sweep: dinv, f -> u
          s += (prm.sweeps_down - 1) * (spmv_bytes(A, format) + 16.0 * n);  // further pre-sweeps
-         s += prm.sweeps_up * (spmv_bytes(A, format) + 16.0 * n);          // post-sweeps
+         s += (prm.sweeps_up - (levels[l].folded ? 1 : 0)) * (spmv_bytes(A, format) + 16.0 * n); // post-sweeps (a folded level: all but the first)
       }
       s += spmv_bytes(A, format) + 8.0 * n;                             // residual
       s += spmv_bytes(levels[l].R, format);                             // restriction
-      s += spmv_bytes(levels[l].P, format) + 8.0 * n;                   // prolongation-add
+      // folded up leg (counted whenever the level is folded, also for a cycle run with HDA_FOLD_UP=0): P~, e -> out in spmv_bytes, and
+      // 32 n as the accounting was specified -- the kernel reads u, t and dinv per row, 24 n, so this is 8 n per level on the safe side
+      if (levels[l].folded) s += spmv_bytes(levels[l].Pt, format) + 32.0 * n;
+      else s += spmv_bytes(levels[l].P, format) + 8.0 * n;              // prolongation-add
    }
    if (tail) s += tail->vcycle_bytes(format) + 16.0 * coarse_n; // replicated coarse levels: every rank does all of it
    else s += 8.0 * coarse_n * coarse_n + 16.0 * coarse_n;
@@ -3947,6 +4025,7 @@ void Amg::cycle(const double *b, double *x, bool zero_guess, int dot_slot, bool 
    const double *f = b;
    bool first_sweep_done = first_sweep_given && zero_guess; // the level's zero-guess Jacobi sweep u = dinv .* f came out of the restriction above it (level 0: of the caller)
    const bool fuse_first = !(getenv("HDA_FUSE_FIRST_SWEEP") && atoi(getenv("HDA_FUSE_FIRST_SWEEP")) == 0); // (read per cycle: the tests switch it inside one process)
+   const bool fold_up    = !(getenv("HDA_FOLD_UP") && atoi(getenv("HDA_FOLD_UP")) == 0);                   // (the same: 0 runs P and the first up sweep as two launches)
    for (int l = 0; l < L - 1; l++)
    {
       const DCsr &A  = level_A(l);
@@ -3996,14 +4075,22 @@ void Amg::cycle(const double *b, double *x, bool zero_guess, int dot_slot, bool 
       if (l == 0) a = (c == x) ? levels[0].u2.data() : x;
       else a = (c == lv.u.data()) ? lv.u2.data() : lv.u.data();
       const double *fl = (l == 0) ? b : lv.f.data();
-      spmv(lv.P, 1.0, sol[l + 1], 1.0, c, c, &lv.hP);
+      int s0 = 0;
+      if (lv.folded && fold_up)
+      { // prolongation and first Jacobi sweep in one pass over P~ (fold_level): reads the coarse correction, the iterate c and the
+        // residual t the down leg left (nothing has touched either since), writes a
+         jacobi_folded(level_A(l), lv.Pt, sweep_dinv(l, 1, 0), lv.t.data(), sol[l + 1], c, a);
+         std::swap(c, a);
+         s0 = 1;
+      }
+      else spmv(lv.P, 1.0, sol[l + 1], 1.0, c, c, &lv.hP);
       if (dist && lv.pg_ready)
       { // the ghost copies of the iterate take the correction of their own P rows (the coarse ghosts have just been refreshed)
          const int nown = level_A(l).nrows;
          if (lv.Pg.nrows) spmv(lv.Pg, 1.0, sol[l + 1], 1.0, c + nown, c + nown);
          ghosts_fresh_ = true;
       }
-      for (int s = 0; s < prm.sweeps_up; s++)
+      for (int s = s0; s < prm.sweeps_up; s++)
       {
          const bool last = (l == 0) && (s == prm.sweeps_up - 1);
          // (same smoother both ways: the same divisors, and on row blocks the same sweep-order copy of them)
@@ -5102,7 +5189,7 @@ void Amg::setup_dist_partitioned(const DCsr &Aloc, const HaloPlan &hA0_, const s
       tail           = std::make_unique<Amg>(prm);
       tail->level0   = l + level0;
       gather_global(Al, part, ghosts, tail->own_A0);
-      tail->setup(tail->own_A0);
+      tail->setup(tail->own_A0, false); // (a replicated tail is not folded: DESIGN section 17)
       for (int t = 1; t < tail->stats_levels && stats_levels < 32; t++, stats_levels++)
       {
          stats_nnz[stats_levels]  = tail->stats_nnz[t];

@@ -1006,13 +1006,31 @@ extern "C" int hda_amg_level_matrix(hda_amg_t h, int level, int which, hda_csr_t
    else
    {
       HDA_REQUIRE(level < h->amg->num_levels() - 1, "no transfer operator on the coarsest level");
-      m = (which == 1) ? &h->amg->level(level).P : &h->amg->level(level).R;
+      HDA_REQUIRE(which >= 1 && which <= 3, "which: 0 operator, 1 P, 2 R, 3 the folded up-leg operator");
+      HDA_REQUIRE(which != 3 || h->amg->level_folded(level), "the up leg of this level is not folded");
+      m = (which == 1) ? &h->amg->level(level).P : (which == 2) ? &h->amg->level(level).R : &h->amg->level(level).Pt;
    }
    auto v      = std::make_unique<hda_csr_s>();
    v->borrowed = true;
    v->ref      = m;
    *out        = v.get();
    h->views.push_back(std::move(v));
+   HDA_CATCH
+}
+extern "C" int hda_amg_fold_sweep(hda_amg_t h, int level, const double *dinv, const double *t, const double *e, const double *u, double *out)
+{
+   HDA_TRY
+   HDA_REQUIRE(h && h->amg && dinv && t && e && u && out, "hda_amg_fold_sweep: null argument");
+   HDA_REQUIRE(h->amg->level_folded(level), "the up leg of this level is not folded");
+   const DCsr    &A = h->amg->level_A(level), &M = h->amg->level(level).Pt;
+   DArray<double> dd, dt, de, du, dout((size_t)M.nrows);
+   dd.upload(dinv, (size_t)M.nrows);
+   dt.upload(t, (size_t)M.nrows);
+   de.upload(e, (size_t)M.ncols);
+   du.upload(u, (size_t)M.nrows);
+   dout.upload(out, (size_t)M.nrows); // rows the sweep leaves alone come back as they were given
+   jacobi_folded(A, M, dd.data(), dt.data(), de.data(), du.data(), dout.data());
+   dout.download(out, (size_t)M.nrows);
    HDA_CATCH
 }
 extern "C" int hda_amg_level_cf(hda_amg_t h, int level, int *cf)

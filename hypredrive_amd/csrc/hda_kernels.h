@@ -32,6 +32,12 @@ void residual(const DCsr &A, const double *x, const double *b, double *out, cons
 // x_out = x_in + dinv .* (b - A*x_in).  dot_slot >= 0 also emits partials of <b, x_out>.
 void jacobi(const DCsr &A, const double *dinv, const double *b, const double *x_in,
             double *x_out, int dot_slot, const HaloPlan *halo = nullptr);
+// The same sweep right after a prolongation, folded.  With t = b - A u left by the down leg and e the coarse
+// correction, u + P e followed by one Jacobi sweep is out = (u + dinv .* t) + Pt e, Pt = P - diag(dinv) (A P): one pass over Pt in place
+// of a pass over P and a pass over A.  Launched as the Jacobi sweep of A (timing probes on (A, Jacobi) see it); out must not alias u.
+// spmv_foldable: the product of Pt runs on a kernel that has the folded form (lane-group, streaming or list-windowed CSR, uncoded)
+void jacobi_folded(const DCsr &A, const DCsr &Pt, const double *dinv, const double *t, const double *e, const double *u, double *out);
+bool spmv_foldable(const DCsr &Pt);
 // first sweep from a zero guess: x = dinv .* b
 void jacobi_zero_guess(int n, const double *dinv, const double *b, double *x);
 

@@ -478,7 +478,10 @@ enum { MODE_PLAIN = 0, MODE_RESID = 1, MODE_JACOBI = 2 };
 //  MODE_PLAIN : out = alpha*Ax + beta*yin       DOT: partial += out_i * w_i
 //  MODE_RESID : out = b - Ax
 //  MODE_JACOBI: out = xin + dinv*(b - A xin)    DOT: partial += b_i * out_i
-template <int LPR, int MODE, bool DOT>
+//  FOLD (MODE_JACOBI, last so that the names of the other instantiations keep their prefix): the sweep after a prolongation in its folded
+//  storage form (jacobi_folded below) -- the matrix is P~ = P - D^-1 (A P), x the coarse correction, yin the row's own iterate, b the
+//  residual left by the down leg: out = (yin + dinv*b) + P~ x
+template <int LPR, int MODE, bool DOT, bool FOLD = false>
 __global__ __launch_bounds__(256) void k_spmv(int n, const int *__restrict__ rowptr,
                                               const int *__restrict__ col,
                                               const double *__restrict__ val,
@@ -490,6 +493,7 @@ __global__ __launch_bounds__(256) void k_spmv(int n, const int *__restrict__ row
                                               double *__restrict__ partial, const double *__restrict__ dinv2 = nullptr,
                                               double *__restrict__ out2 = nullptr)
 { // out2 (MODE_PLAIN): a second result out2 = dinv2 .* out, as in k_spmv_stream
+   static_assert(!FOLD || (MODE == MODE_JACOBI && !DOT), "the folded form exists for the Jacobi sweep without a dot alone");
    const int  lane = threadIdx.x & (LPR - 1);
    const long G    = (long)gridDim.x * (256 / LPR);
    const long gid  = ((long)blockIdx.x * 256 + threadIdx.x) / LPR;
@@ -527,12 +531,12 @@ __global__ __launch_bounds__(256) void k_spmv(int n, const int *__restrict__ row
          else
          {
             const double b0 = b[r0];
-            o0              = x[r0] + dinv[r0] * (b0 - a0);
+            o0              = FOLD ? (yin[r0] + dinv[r0] * b0) + a0 : x[r0] + dinv[r0] * (b0 - a0);
             if (DOT) acc += b0 * o0;
             if (h1)
             {
                const double b1 = b[r1];
-               o1              = x[r1] + dinv[r1] * (b1 - a1);
+               o1              = FOLD ? (yin[r1] + dinv[r1] * b1) + a1 : x[r1] + dinv[r1] * (b1 - a1);
                if (DOT) acc += b1 * o1;
             }
          }
@@ -609,7 +613,8 @@ static void ensure_plan(const DCsr &A)
 // one-byte codes into a 255-entry dictionary held in LDS; code 255 = read the value array
 // SPLIT: row-partitioned product overlapped with its halo exchange -- entries whose column is a ghost (>= nown)
 // contribute nothing here; k_offd_fix adds them once the ghost values have arrived
-template <int MODE, bool DOT, bool VC, bool SPLIT>
+// FOLD (last): the folded Jacobi sweep, as in k_spmv
+template <int MODE, bool DOT, bool VC, bool SPLIT, bool FOLD = false>
 __global__ __launch_bounds__(256) void k_spmv_stream(int nchunks, const int *__restrict__ chunk_row,
                                                      const int *__restrict__ rowptr, const int *__restrict__ col,
                                                      const double *__restrict__ val, const double *__restrict__ x,
@@ -621,6 +626,7 @@ __global__ __launch_bounds__(256) void k_spmv_stream(int nchunks, const int *__r
                                                      double *__restrict__ out2)
 { // out2 (MODE_PLAIN only): a second result out2 = dinv2 .* out -- the zero-guess Jacobi sweep of the next coarser level rides
   // on the restriction that produces its right-hand side
+   static_assert(!FOLD || (MODE == MODE_JACOBI && !DOT && !VC && !SPLIT), "the folded form exists for the whole Jacobi sweep without a dot alone");
    extern __shared__ double prod[];
    __shared__ double sdict[VC ? 256 : 1];
    const int tid  = threadIdx.x;
@@ -700,7 +706,7 @@ for (; k + 768 < k1; k += 1024)
             else
             {
                const double br = b[r];
-               o0              = x[r] + dinv[r] * (br - sum);
+               o0              = FOLD ? (yin[r] + dinv[r] * br) + sum : x[r] + dinv[r] * (br - sum);
                if (DOT) acc += br * o0;
             }
             out[r] = o0;
@@ -1489,7 +1495,9 @@ static void ensure_window(const DCsr &A)
 // registers, i.e. from an allocation of 80 to one of 96 per wave, and from 0.215 to 0.349 ms per level-0 transfer product at 256^3 with
 // the same instructions, vector registers, LDS and traffic (profiles/transfer_kernels.md: the allocation is the one column of the kernel
 // trace that differs between the fast and the slow arms).  No instantiation may cross that line again unnoticed.
-template <int MODE, bool DOT, bool VC, bool SPLIT, bool RUNS = false, bool EPI = false>
+// FOLD (last, for the same reason): the folded Jacobi sweep, as in k_spmv -- the row's own iterate comes from yin and travels one
+// chunk ahead in the place of x[r]
+template <int MODE, bool DOT, bool VC, bool SPLIT, bool RUNS = false, bool EPI = false, bool FOLD = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_spmv_win(int nw, const int *__restrict__ wmeta, const int *__restrict__ rowptr,
                                                   const unsigned short *__restrict__ lidx, const int *__restrict__ ucol,
                                                   const double *__restrict__ val, const double *__restrict__ x, double alpha, double beta,
@@ -1499,6 +1507,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_sp
                                                   const double *__restrict__ dinv2 = nullptr, double *__restrict__ out2 = nullptr)
 { // out2 (EPI, MODE_PLAIN only): a second result out2 = dinv2 .* out, as in k_spmv_stream (the next level's zero-guess Jacobi sweep)
    static_assert(!EPI || (MODE == MODE_PLAIN && !DOT && !SPLIT), "the scaled second result exists for whole plain products only");
+   static_assert(!FOLD || (MODE == MODE_JACOBI && !DOT && !VC && !SPLIT && !RUNS), "the folded form exists for the whole Jacobi sweep on the list form alone");
    extern __shared__ double smem[];
    double *prod = smem, *xs = smem + prod_len;
    __shared__ double sdict[VC ? 256 : 1];
@@ -1551,7 +1560,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_sp
          pe          = rowptr[r + 1] - c.k0;
          if (MODE == MODE_PLAIN) { if (beta != 0.0) pb = yin[r]; if (DOT) pd = w[r]; if (EPI) pd = dinv2[r]; } // (EPI: never with DOT)
          else if (MODE == MODE_RESID) pb = b[r];
-         else { pb = b[r]; pd = dinv[r]; px = x[r]; }
+         else { pb = b[r]; pd = dinv[r]; px = FOLD ? yin[r] : x[r]; }
       }
    };
    auto request = [&](const Chunk &c) {
@@ -1662,7 +1671,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_sp
             else
             {
                const double br = first ? cb : b[r];
-               o0              = (first ? cx : x[r]) + (first ? cd : dinv[r]) * (br - sum);
+               if (FOLD) o0 = ((first ? cx : yin[r]) + (first ? cd : dinv[r]) * br) + sum;
+               else o0 = (first ? cx : x[r]) + (first ? cd : dinv[r]) * (br - sum);
                if (DOT) acc += br * o0;
             }
             out[r] = o0;
@@ -1985,6 +1995,15 @@ struct SpmvEpilogue {
    bool          done  = false;
 };
 #define g_epilogue (RankState<SpmvEpilogue>::get())
+// The Jacobi sweep after a prolongation in its folded storage form (jacobi_folded): for the one launch it is armed for, the sweep of
+// A streams M = P~ = P - D^-1 (A P) instead of A -- x is then the coarse correction and yin the row's own iterate.  The launch stays
+// a MODE_JACOBI launch on A: a probe armed on (A, Jacobi) brackets it like any other sweep of that operator
+struct SpmvFold {
+   const DCsr *M    = nullptr;
+   bool        done = false;
+};
+#define g_fold (RankState<SpmvFold>::get())
+static bool fold_form(SpmvForm f, const DCsr &M) { return (f == SpmvForm::LaneGroup || f == SpmvForm::Stream || f == SpmvForm::Window) && M.coded != 2; }
 
 // The kernel a product of A runs on (whole product, or the owned-column half of a split one), decided as launch_spmv_impl
 // launches: builds the plans it needs (chunk plan, stencil / value coding, windows) on first use.  hda_csr_form reports it.
@@ -2008,13 +2027,19 @@ static SpmvForm spmv_form(const DCsr &A, bool split)
 }
 
 template <int MODE, bool DOT>
-static bool launch_spmv_impl(const DCsr &A, const double *x, double alpha, double beta,
+static bool launch_spmv_impl(const DCsr &A_in, const double *x, double alpha, double beta,
                         const double *yin, const double *b, const double *dinv, const double *w,
                         double *out, double *partial, int nown = -1)
 {
-   if (A.nrows == 0 && !DOT) return true;
+   // (FOLD exists for the whole Jacobi sweep without a dot alone: the constant keeps every other MODE / DOT from instantiating it)
+   constexpr bool kFold = MODE == MODE_JACOBI && !DOT;
    const bool     split = nown >= 0;
+   const bool     fold  = kFold && !split && g_fold.M;
+   const DCsr    &A     = fold ? *g_fold.M : A_in; // the matrix this launch streams
+   if (fold) g_fold.done = true;
+   if (A.nrows == 0 && !DOT) return true;
    const SpmvForm form  = spmv_form(A, split);
+   HDA_REQUIRE(!fold || fold_form(form, A), "folded sweep armed on an operator whose storage form has no folded kernel");
    const int      gmax  = split ? overlap_grid() : kRedBlocks;
    if (form == SpmvForm::RowClass || form == SpmvForm::Coded)
    {
@@ -2058,10 +2083,11 @@ static bool launch_spmv_impl(const DCsr &A, const double *x, double alpha, doubl
             wepi_o = g_epilogue.out2;
             g_epilogue.done = true;
          }
-#define HDA_WIN(VCF, SPF, RUNF, EPIF, CODE, DICT)                                                                                                \
-   k_spmv_win<MODE, DOT, VCF, SPF, RUNF, EPIF><<<wg, 256, wlds, STREAM>>>(A.nwin, A.wmeta.data(), A.rowptr.data(), A.lidx.data(), A.ucol.data(),  \
-                                                                          A.val.data(), x, alpha, beta, yin, b, dinv, w, out, partial, nown,     \
-                                                                          plen, CODE, DICT, win_pf(), wepi_d, wepi_o)
+#define HDA_WIN(VCF, SPF, RUNF, EPIF, CODE, DICT) HDA_WINF(VCF, SPF, RUNF, EPIF, false, CODE, DICT)
+#define HDA_WINF(VCF, SPF, RUNF, EPIF, FOLDF, CODE, DICT)                                                                                        \
+   k_spmv_win<MODE, DOT, VCF, SPF, RUNF, EPIF, FOLDF><<<wg, 256, wlds, STREAM>>>(A.nwin, A.wmeta.data(), A.rowptr.data(), A.lidx.data(),         \
+                                                                                 A.ucol.data(), A.val.data(), x, alpha, beta, yin, b, dinv, w,  \
+                                                                                 out, partial, nown, plen, CODE, DICT, win_pf(), wepi_d, wepi_o)
          // (EPI exists for whole plain products without a dot alone: the constant keeps every other MODE / DOT from instantiating it)
          constexpr bool kEpi = MODE == MODE_PLAIN && !DOT;
          if (form == SpmvForm::WindowRuns)
@@ -2080,9 +2106,11 @@ static bool launch_spmv_impl(const DCsr &A, const double *x, double alpha, doubl
          {
             if (split) { HDA_WIN(false, true, false, false, nullptr, nullptr); }
             else if (wepi) { HDA_WIN(false, false, false, kEpi, nullptr, nullptr); }
+            else if (fold) { HDA_WINF(false, false, false, false, kFold, nullptr, nullptr); }
             else { HDA_WIN(false, false, false, false, nullptr, nullptr); }
          }
 #undef HDA_WIN
+#undef HDA_WINF
          return true;
       }
       const int    grid = DOT ? gmax : std::min(gmax, ((A.nchunks + 7) / 8) * 8);
@@ -2096,9 +2124,11 @@ static bool launch_spmv_impl(const DCsr &A, const double *x, double alpha, doubl
          epi_o = g_epilogue.out2;
          g_epilogue.done = true;
       }
-#define HDA_STREAM(VCF, SPF, CODE, DICT)                                                                                                  \
-   k_spmv_stream<MODE, DOT, VCF, SPF><<<grid, 256, lds, STREAM>>>(A.nchunks, A.chunk_row.data(), A.rowptr.data(), A.col.data(), A.val.data(), x, \
-                                                                  alpha, beta, yin, b, dinv, w, out, partial, CODE, DICT, nown, epi_d, epi_o)
+#define HDA_STREAM(VCF, SPF, CODE, DICT) HDA_STREAMF(VCF, SPF, false, CODE, DICT)
+#define HDA_STREAMF(VCF, SPF, FOLDF, CODE, DICT)                                                                                           \
+   k_spmv_stream<MODE, DOT, VCF, SPF, FOLDF><<<grid, 256, lds, STREAM>>>(A.nchunks, A.chunk_row.data(), A.rowptr.data(), A.col.data(),      \
+                                                                         A.val.data(), x, alpha, beta, yin, b, dinv, w, out, partial, CODE, \
+                                                                         DICT, nown, epi_d, epi_o)
       if (A.coded == 2)
       {
          if (split) HDA_STREAM(true, true, A.code.data(), A.dict_val.data());
@@ -2107,9 +2137,11 @@ static bool launch_spmv_impl(const DCsr &A, const double *x, double alpha, doubl
       else
       {
          if (split) HDA_STREAM(false, true, nullptr, nullptr);
+         else if (fold) HDA_STREAMF(false, false, kFold, nullptr, nullptr);
          else HDA_STREAM(false, false, nullptr, nullptr);
       }
 #undef HDA_STREAM
+#undef HDA_STREAMF
       return true;
    }
    if (form == SpmvForm::None) return false; // the lane-group kernel (very long rows, HDA_SPMV=vector) has no split form: caller exchanges first
@@ -2124,10 +2156,17 @@ static bool launch_spmv_impl(const DCsr &A, const double *x, double alpha, doubl
       vepi_o = g_epilogue.out2;
       g_epilogue.done = true;
    }
-#define HDA_LAUNCH(L)                                                                         \
-   k_spmv<L, MODE, DOT><<<grid, 256, 0, STREAM>>>(A.nrows, A.rowptr.data(), A.col.data(),      \
-                                                  A.val.data(), x, alpha, beta, yin, b, dinv,  \
-                                                  w, out, partial, vepi_d, vepi_o)
+#define HDA_LAUNCH(L)                                                                                   \
+   do {                                                                                                 \
+      if (fold)                                                                                         \
+         k_spmv<L, MODE, DOT, kFold><<<grid, 256, 0, STREAM>>>(A.nrows, A.rowptr.data(), A.col.data(),   \
+                                                               A.val.data(), x, alpha, beta, yin, b,    \
+                                                               dinv, w, out, partial, vepi_d, vepi_o);  \
+      else                                                                                              \
+         k_spmv<L, MODE, DOT><<<grid, 256, 0, STREAM>>>(A.nrows, A.rowptr.data(), A.col.data(),          \
+                                                        A.val.data(), x, alpha, beta, yin, b, dinv,     \
+                                                        w, out, partial, vepi_d, vepi_o);               \
+   } while (0)
    switch (lpr)
    {
       case 4: HDA_LAUNCH(4); break;
@@ -2334,6 +2373,25 @@ void jacobi(const DCsr &A, const double *dinv, const double *b, const double *x_
       launch_spmv<MODE_JACOBI, true>(A, halo, x_in, 1.0, 0.0, nullptr, b, dinv, nullptr, x_out, Context::get().slot(dot_slot));
    else
       launch_spmv<MODE_JACOBI, false>(A, halo, x_in, 1.0, 0.0, nullptr, b, dinv, nullptr, x_out, nullptr);
+}
+
+namespace {
+struct FoldArmed { // disarmed on every way out, like EpilogueArmed
+   explicit FoldArmed(const DCsr *M) { g_fold = SpmvFold{M, false}; }
+   ~FoldArmed() { g_fold = SpmvFold{}; }
+};
+} // namespace
+bool spmv_foldable(const DCsr &Pt)
+{
+   if (Pt.nrows == 0 || Pt.nnz == 0) return false;
+   return fold_form(spmv_form(Pt, false), Pt);
+}
+void jacobi_folded(const DCsr &A, const DCsr &Pt, const double *dinv, const double *t, const double *e, const double *u, double *out)
+{
+   HDA_REQUIRE(Pt.nrows == A.nrows, "folded sweep: P~ has the rows of the level's operator");
+   FoldArmed armed(&Pt);
+   launch_spmv<MODE_JACOBI, false>(A, nullptr, e, 1.0, 0.0, u, t, dinv, nullptr, out, nullptr);
+   HDA_REQUIRE(g_fold.done, "folded sweep: the launch did not take the fold");
 }
 
 // ---- test entries of the product family (hda_csr_form, hda_spmv_mode)

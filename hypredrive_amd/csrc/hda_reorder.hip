@@ -190,6 +190,7 @@ void Amg::reorder_levels()
       const int nl = nown(l), nn = nown(l + 1);
       permute_csr(lv.A, pl, rl, nl);                  // A_l: rows and owned columns
       permute_csr(lv.P, pl, rn, nn);                  // P_l: rows level l, columns level l+1
+      if (lv.Pt.nrows) permute_csr(lv.Pt, pl, rn, nn); // A_l P_l kept for the folded up leg: exactly like P_l
       if (lv.pg_ready && lv.Pg.nrows && rn) permute_csr(lv.Pg, nullptr, rn, nn); // its ghost rows keep their slots, owned columns move
       permute_csr(lv.R, pn, rl, nl);                  // R_l: rows level l+1, columns level l
       if (dist)

@@ -264,8 +264,12 @@ int hda_ilu_factors(hda_amg_t h, int level, hda_csr_t *out);
  * tier 0: the setup's inverses; 1 (b <= 8) / 2: recomputed by that kernel tier.  *b = 0: the level built no blocks. */
 int hda_mgr_blk_inverses(hda_amg_t h, int level, int tier, double *out, int *b, int *nf);
 int hda_amg_num_levels(hda_amg_t h);
-/* which: 0 = A_l, 1 = P_l, 2 = R_l; returns a borrowed handle (do not destroy) */
+/* which: 0 = A_l, 1 = P_l, 2 = R_l, 3 = P~_l = P_l - diag(dinv_up) (A_l P_l) of a level whose up leg is folded (an error on
+ * every other level); returns a borrowed handle (do not destroy) */
 int hda_amg_level_matrix(hda_amg_t h, int level, int which, hda_csr_t *out);
+/* Test entry: the folded up-leg sweep of a folded level on vectors of the caller, launched as the cycle launches it:
+ * out = (u + dinv .* t) + P~_l e.  dinv, t, u, out: rows of level l; e: rows of level l + 1.  An error on a level that is not folded. */
+int hda_amg_fold_sweep(hda_amg_t h, int level, const double *dinv, const double *t, const double *e, const double *u, double *out);
 int hda_amg_level_cf(hda_amg_t h, int level, int *cf);
 /* row blocks the setup worked with (hda_amg_params.blocks resolved; 1 = none) and a level's block starts (blocks + 1 values) */
 int hda_amg_blocks(hda_amg_t h);
