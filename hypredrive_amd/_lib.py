@@ -95,6 +95,7 @@ SYMBOLS = [
     "hda_cljp", "hda_rs_blocks", "hda_falgout_blocks", "hda_measure_rnd",
     "hda_schwarz_create", "hda_schwarz_domains", "hda_schwarz_info", "hda_precond_time",
     "hda_spgemm_last_route", "hda_sort_rows_last_route",
+    "hda_ams_default_amg_params", "hda_ams_create", "hda_ams_matrix", "hda_ams_info",
 ]
 
 
@@ -195,6 +196,11 @@ def load():
     L.hda_schwarz_domains.argtypes = [vp, P(C.c_int), ip, ip]
     L.hda_schwarz_info.argtypes = [vp, P(C.c_int64), P(C.c_double)]
     L.hda_precond_time.argtypes = [vp, C.c_int, P(C.c_double)]
+    L.hda_ams_default_amg_params.argtypes = [P(AmgParams), C.c_int]
+    L.hda_ams_default_amg_params.restype = None
+    L.hda_ams_create.argtypes = [vp, vp, dp, dp, dp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, P(AmgParams), P(AmgParams), P(vp)]
+    L.hda_ams_matrix.argtypes = [vp, C.c_int, P(vp)]
+    L.hda_ams_info.argtypes = [vp, P(C.c_int64), P(C.c_double)]
     L.hda_set_overlap.argtypes = [C.c_int]
     L.hda_set_overlap.restype = None
     L.hda_amg_num_levels.argtypes = [vp]
@@ -806,8 +812,74 @@ class Schwarz:
         return z
 
 
+class Ams:
+    """'preconditioner: ams': the auxiliary-space Maxwell preconditioner for A (n_e x n_e) with the discrete gradient
+    G (n_e x n_v, a Csr) and coords = the vertex coordinate vectors; usable as amg= in pcg()/gmres()/fgmres()/bicgstab().
+    alpha / beta: AmgParams of the BoomerAMG on Pi^T A Pi / G^T A G (None = Ams.amg_params)."""
+
+    def __init__(self, A, G, coords, dimension=3, cycle_type=1, relax_times=1, relax_weight=1.0, alpha=None, beta=None, max_iter=1):
+        self.A, self.G = A, G
+        nv = G.ncols
+        c = [np.ascontiguousarray(v, dtype=np.float64) for v in coords]
+        while len(c) < 3:
+            c.append(np.zeros(nv))
+        assert all(v.size == nv for v in c), "one coordinate per column of G"
+        self.alpha = alpha if alpha is not None else Ams.amg_params(dimension)
+        self.beta = beta if beta is not None else Ams.amg_params(1)
+        self.h = C.c_void_p()
+        _check(load().hda_ams_create(A.h, G.h, _dp(c[0]), _dp(c[1]), _dp(c[2]), dimension, cycle_type, relax_times, relax_weight, max_iter,
+                                     C.byref(self.alpha), C.byref(self.beta), C.byref(self.h)))
+
+    @staticmethod
+    def amg_params(num_functions=1, **kw):
+        """AmgParams of a subspace solver: the reference's GPU-build AMS defaults with the free parameters of DESIGN section 18"""
+        p = AmgParams()
+        load().hda_ams_default_amg_params(C.byref(p), num_functions)
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise KeyError(k)
+            setattr(p, k, v)
+        return p
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            load().hda_amg_destroy(self.h)
+            self.h = None
+
+    def _matrix(self, which):
+        out = C.c_void_p()
+        _check(load().hda_ams_matrix(self.h, which, C.byref(out)))
+        return Csr(out, owned=False, keep=self)
+
+    def pi(self):
+        return self._matrix(0)
+
+    def a_g(self):
+        """G^T A G after the zero-row repair"""
+        return self._matrix(1)
+
+    def a_pi(self):
+        """Pi^T A Pi after the zero-row repair"""
+        return self._matrix(2)
+
+    def info(self):
+        """dict: n_e, n_v, nnz_pi, nnz_a_g, nnz_a_pi, fixed_rows_g, fixed_rows_pi, levels_g, levels_pi, setup_ms, apply_bytes"""
+        v, ms = (C.c_int64 * 8)(), (C.c_double * 5)()
+        _check(load().hda_ams_info(self.h, v, ms))
+        return dict(n_e=v[0], n_v=v[1], nnz_pi=v[2], nnz_a_g=v[3], nnz_a_pi=v[4], fixed_rows_g=v[5], fixed_rows_pi=v[6],
+                    levels_g=v[7] // 256, levels_pi=v[7] % 256,
+                    setup_ms=dict(pi=ms[0], products=ms[1], b_g=ms[2], b_pi=ms[3]), apply_bytes=ms[4])
+
+    def apply(self, r):
+        """One application from a zero guess (max_iter cycles)."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        z = np.zeros_like(r)
+        _check(load().hda_amg_vcycle(self.h, _dp(r), _dp(z)))
+        return z
+
+
 def precond_time(M, reps=20):
-    """Average device ms of one application of an Ilu / Schwarz handle (vectors stay on the device)."""
+    """Average device ms of one application of an Ilu / Schwarz / Ams handle (vectors stay on the device)."""
     ms = C.c_double()
     _check(load().hda_precond_time(M.h, reps, C.byref(ms)))
     return ms.value

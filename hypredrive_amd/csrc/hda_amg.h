@@ -384,6 +384,47 @@ class Amg {
    bool                  coarse_dense = false;
 };
 
+// ---- AMS (hda_ams.hip): auxiliary-space Maxwell preconditioner on one rank.  Parameter contract: reference AMS_args
+// (src/internal/ams.c:37-63) as hypredrv_AMSCreate forwards them to the HYPRE_AMSSet* setters.
+struct AmsAmgOptions { // HYPRE_AMSSetAlphaAMGOptions / SetBetaAMGOptions + ...CoarseRelaxType; defaults: the reference's GPU build
+   int    coarsen_type = 8, agg_levels = 1, relax_type = 18;
+   double strength_threshold = 0.25;
+   int    interp_type = 6, pmax = 4, coarse_relax_type = 18;
+};
+struct AmsParams {
+   int           dimension = 3, max_iter = 1, cycle_type = 1, relax_type = 1, relax_times = 1;
+   double        tolerance = 0.0, relax_weight = 1.0;
+   AmgParams     alpha, beta; // B_Pi on Pi^T A Pi (num_functions = dimension is set by the setup), B_G on G^T A G: see ams_subspace_amg
+};
+const char *ams_cycle_string(int cycle_type);                           // "01210" ...; nullptr: a cycle that is not built
+std::string ams_refusal(const AmsParams &p);                            // why this selection is not built, by key name; empty = built
+AmgParams   ams_subspace_amg(const AmsAmgOptions &o, int num_functions); // the BoomerAMG of a subspace, free parameters included
+// Pi (n_e x d n_v) from G and g_k = G c_k (device vectors of n_e entries); rows keep G's column order, k fastest
+void ams_build_pi(const DCsr &G, int d, const double *const g[3], DCsr &Pi);
+// rows of the square matrix C without a non-zero value become the unit diagonal; returns how many
+int  ams_fix_zero_rows(DCsr &C);
+class Ams {
+ public:
+   // A is borrowed and must outlive the object, G is copied; coords: d device vectors of G.ncols entries, read by the setup only
+   void        setup(const DCsr &A, const DCsr &G, const double *const coords[3], const AmsParams &p);
+   void        apply(const double *r, double *z); // z = M r from z = 0: max_iter cycles; r and z must not alias
+   const DCsr &pi() const { return Pi; }
+   const DCsr &a_g() const { return A_G; }
+   const DCsr &a_pi() const { return A_Pi; }
+   Amg        &b_g() { return *B_G; }
+   Amg        &b_pi() { return *B_Pi; }
+   double      apply_bytes() const; // algorithmic HBM bytes of one application (CSR figure)
+   AmsParams   prm;
+   int         n_e = 0, n_v = 0, fixed_rows[2] = {0, 0}; // repaired rows of A_G / A_Pi
+   double      setup_ms[4] = {0, 0, 0, 0};               // Pi and transposes, products and repair, B_G, B_Pi (host wall time, device synced)
+
+ private:
+   const DCsr          *A = nullptr;
+   DCsr                 G, Pi, GT, PiT, A_G, A_Pi;
+   std::unique_ptr<Amg> B_G, B_Pi;
+   DArray<double>       dinv, t, z2, rg, eg, rp, ep;
+};
+
 // row-partitioned sparse product and reverse halo sum (hda_amg_setup.hip), shared by the partitioned setups
 void dist_spgemm(const DCsr &X, const HaloPlan &hX, const DCsr &Y, const std::vector<long long> &y_ghosts,
                  const std::vector<long long> &part_c, DCsr &C, std::vector<long long> &c_ghosts);
@@ -557,6 +598,9 @@ void amg_interp_one_point(const DCsr &A, const unsigned char *smask, const int *
 bool        amg_agg_interp_type_built(int t);
 const char *amg_agg_interp_name(int t);
 std::string amg_agg_interp_refusal(int t);
+// the relaxation types the cycle runs (coarse: those and Gaussian elimination, 9), and the refusal of the others
+bool        amg_relax_type_built(int t, bool coarse = false);
+const char *amg_relax_refusal(bool coarse);
 // the prolongation types amg_interp_extpi builds, and the refusal of the others by name
 bool        amg_interp_type_built(int t);
 std::string amg_interp_refusal(int t);

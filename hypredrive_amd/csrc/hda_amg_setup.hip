@@ -3178,6 +3178,17 @@ const double *Amg::sweep_dinv(int l, int dir, int s)
    return (dir == 0 || same_divisors(prm.relax_up, prm.relax_down)) ? lv.dinv_down.data() : lv.dinv_up.data();
 }
 
+bool amg_relax_type_built(int t, bool coarse)
+{
+   return is_jacobi_type(t) || is_gs_type(t) || is_two_stage_type(t) || t == 16 || (coarse && t == 9);
+}
+const char *amg_relax_refusal(bool coarse)
+{
+   return coarse ? "coarse relaxation must be Gaussian elimination (9), Jacobi, hybrid or two-stage Gauss-Seidel or Chebyshev"
+                 : "device V-cycle implements Jacobi (0, 7, 18), hybrid Gauss-Seidel (3, 4, 6, 8, 13, 14), two-stage Gauss-Seidel (11, 12) and "
+                   "Chebyshev (16) smoothers";
+}
+
 void Amg::build_hierarchy(const DCsr &A, bool keep_ap)
 {
    HDA_REQUIRE(amg_coarsen_type_built(prm.coarsen_type), amg_coarsen_refusal(prm.coarsen_type).c_str());
@@ -3189,12 +3200,8 @@ void Amg::build_hierarchy(const DCsr &A, bool keep_ap)
    // own (denominators over the strong C neighbours of the intermediate point, no sign filter), built from sparse products
    HDA_REQUIRE(amg_interp_type_built(prm.interp_type), amg_interp_refusal(prm.interp_type).c_str());
    HDA_REQUIRE(prm.interp_type != 4 || prm.num_functions <= 1, "multipass interpolation (prolongation_type 4) is implemented on a scalar problem only");
-   auto known = [](int t) { return is_jacobi_type(t) || is_gs_type(t) || is_two_stage_type(t) || t == 16; };
-   HDA_REQUIRE(known(prm.relax_down) && known(prm.relax_up),
-               "device V-cycle implements Jacobi (0, 7, 18), hybrid Gauss-Seidel (3, 4, 6, 8, 13, 14), two-stage Gauss-Seidel (11, 12) and "
-               "Chebyshev (16) smoothers");
-   HDA_REQUIRE(prm.relax_coarse == 9 || known(prm.relax_coarse),
-               "coarse relaxation must be Gaussian elimination (9), Jacobi, hybrid or two-stage Gauss-Seidel or Chebyshev");
+   HDA_REQUIRE(amg_relax_type_built(prm.relax_down) && amg_relax_type_built(prm.relax_up), amg_relax_refusal(false));
+   HDA_REQUIRE(amg_relax_type_built(prm.relax_coarse, true), amg_relax_refusal(true));
    HDA_REQUIRE(prm.cheby_variant == 0 || (prm.relax_down != 16 && prm.relax_up != 16 && prm.relax_coarse != 16),
                "Chebyshev smoother: only variant 0 (the standard polynomial) is implemented");
    HDA_REQUIRE(prm.agg_num_levels <= 0 || amg_agg_interp_type_built(prm.agg_interp_type), amg_agg_interp_refusal(prm.agg_interp_type).c_str());

@@ -26,6 +26,7 @@ struct hda_amg_s {
    std::unique_ptr<Ilu>                    ilu; // handle made by hda_ilu_create: the preconditioner is one ILU solve
    std::unique_ptr<Mgr>                    mgr; // handle made by hda_mgr_create: the preconditioner is one MGR solve
    std::unique_ptr<Schwarz>                schwarz; // handle made by hda_schwarz_create: one Schwarz solve (work vectors: ilu_r / ilu_c)
+   std::unique_ptr<Ams>                    ams; // handle made by hda_ams_create: one AMS application
    DArray<double>                          ilu_r, ilu_c;
    hda_csr_t                               A = nullptr;
    std::vector<std::unique_ptr<hda_csr_s>> views;
@@ -102,9 +103,9 @@ extern "C" int hda_marker(int id)
    HDA_CATCH
 }
 
-extern "C" void hda_amg_default_params(hda_amg_params *p)
+// the C struct of a parameter set: the mirror of to_params below (max_iter, tol and print_level have no field: one cycle, no test)
+static void from_params(const AmgParams &d, hda_amg_params *p)
 {
-   AmgParams d;
    p->coarsen_type = d.coarsen_type; p->interp_type = d.interp_type; p->pmax = d.pmax;
    p->trunc_factor = d.trunc_factor; p->strong_th = d.strong_th; p->max_row_sum = d.max_row_sum;
    p->max_coarse_size = d.max_coarse_size; p->min_coarse_size = d.min_coarse_size; p->max_levels = d.max_levels;
@@ -123,6 +124,7 @@ extern "C" void hda_amg_default_params(hda_amg_params *p)
    p->blocks = d.blocks; p->block_part = nullptr;
    p->struct_size = (int)sizeof(hda_amg_params);
 }
+extern "C" void hda_amg_default_params(hda_amg_params *p) { from_params(AmgParams(), p); }
 extern "C" void hda_krylov_default_params(hda_krylov_params *p, int gmres)
 {
    p->max_iter = gmres ? 300 : 100; p->rtol = 1.0e-6; p->atol = 0.0; p->two_norm = 1; p->krylov_dim = 30;
@@ -848,17 +850,80 @@ extern "C" int hda_schwarz_info(hda_amg_t h, int64_t info[6], double setup_ms[4]
       for (int q = 0; q < 4; q++) setup_ms[q] = S.setup_ms[q];
    HDA_CATCH
 }
+// "preconditioner: ams" (reference src/internal/ams.c): auxiliary-space Maxwell preconditioner (hda_ams.hip)
+extern "C" void hda_ams_default_amg_params(hda_amg_params *p, int num_functions)
+{
+   AmsAmgOptions o;
+   o.agg_levels = 0; // (the reference's own default, 1, is refused for alpha: see ams_refusal)
+   from_params(ams_subspace_amg(o, num_functions), p);
+}
+extern "C" int hda_ams_create(hda_csr_t A, hda_csr_t G, const double *c0, const double *c1, const double *c2, int dimension, int cycle_type,
+                              int relax_times, double relax_weight, int max_iter, const hda_amg_params *alpha, const hda_amg_params *beta,
+                              hda_amg_t *out)
+{
+   HDA_TRY
+   HDA_REQUIRE(A && G && out && c0 && c1, "hda_ams_create: null argument");
+   HDA_REQUIRE(dimension == 2 || c2, "hda_ams_create: the third coordinate vector is required in three dimensions");
+   hda_amg_params da, db;
+   hda_ams_default_amg_params(&da, dimension);
+   hda_ams_default_amg_params(&db, 1);
+   AmsParams p;
+   p.dimension = dimension; p.cycle_type = cycle_type; p.relax_times = relax_times; p.relax_weight = relax_weight; p.max_iter = max_iter;
+   p.alpha = to_params(alpha ? alpha : &da);
+   p.beta  = to_params(beta ? beta : &db);
+   const DCsr    &g = G->get();
+   DArray<double> c[3];
+   const double  *hc[3] = {c0, c1, c2}, *dc[3] = {nullptr, nullptr, nullptr};
+   for (int k = 0; k < dimension && k < 3; k++)
+   {
+      c[k].upload(hc[k], (size_t)std::max(g.ncols, 0));
+      dc[k] = c[k].data();
+   }
+   auto h = std::make_unique<hda_amg_s>();
+   h->A   = A;
+   h->ams = std::make_unique<Ams>();
+   h->ams->setup(A->get(), g, dc, p);
+   *out = h.release();
+   HDA_CATCH
+}
+extern "C" int hda_ams_matrix(hda_amg_t h, int which, hda_csr_t *out)
+{
+   HDA_TRY
+   HDA_REQUIRE(h && h->ams && out, "not an AMS handle");
+   HDA_REQUIRE(which >= 0 && which <= 2, "which: 0 Pi, 1 G^T A G, 2 Pi^T A Pi");
+   auto v      = std::make_unique<hda_csr_s>();
+   v->borrowed = true;
+   v->ref      = (which == 0) ? &h->ams->pi() : (which == 1) ? &h->ams->a_g() : &h->ams->a_pi();
+   *out        = v.get();
+   h->views.push_back(std::move(v));
+   HDA_CATCH
+}
+extern "C" int hda_ams_info(hda_amg_t h, int64_t info[8], double ms[5])
+{
+   HDA_TRY
+   HDA_REQUIRE(h && h->ams && info, "not an AMS handle");
+   Ams &S  = *h->ams;
+   info[0] = S.n_e; info[1] = S.n_v; info[2] = S.pi().nnz; info[3] = S.a_g().nnz; info[4] = S.a_pi().nnz;
+   info[5] = S.fixed_rows[0]; info[6] = S.fixed_rows[1]; info[7] = 256 * S.b_g().num_levels() + S.b_pi().num_levels();
+   if (ms)
+   {
+      for (int q = 0; q < 4; q++) ms[q] = S.setup_ms[q];
+      ms[4] = S.apply_bytes();
+   }
+   HDA_CATCH
+}
 extern "C" int hda_precond_time(hda_amg_t h, int reps, double *avg_ms)
 {
    HDA_TRY
-   HDA_REQUIRE(h && (h->ilu || h->schwarz) && avg_ms && reps > 0, "hda_precond_time: an ILU or Schwarz handle and reps > 0 are needed");
+   HDA_REQUIRE(h && (h->ilu || h->schwarz || h->ams) && avg_ms && reps > 0, "hda_precond_time: an ILU, Schwarz or AMS handle and reps > 0 are needed");
    Context       &ctx = Context::get();
    const DCsr    &m   = h->A->get();
    const size_t   nv  = (size_t)std::max(std::max(m.ncols, m.nrows), 1);
    DArray<double> b(nv), x(nv);
    fill((int)nv, 0.5, b.data());
    auto launch = [&]() {
-      if (h->schwarz) schwarz_solve(*h->schwarz, m, b.data(), x.data(), true, h->ilu_r, h->ilu_c);
+      if (h->ams) h->ams->apply(b.data(), x.data());
+      else if (h->schwarz) schwarz_solve(*h->schwarz, m, b.data(), x.data(), true, h->ilu_r, h->ilu_c);
       else ilu_solve(*h->ilu, m, nullptr, b.data(), x.data(), true, h->ilu_r, h->ilu_c);
    };
    for (int w = 0; w < 3; w++) launch();
@@ -1073,6 +1138,16 @@ extern "C" int hda_amg_vcycle(hda_amg_t h, const double *b, double *x)
       gs_free_check();
       return HDA_OK;
    }
+   if (h->ams)
+   { // one application of the AMS preconditioner from a zero guess
+      const DCsr    &m = h->A->get();
+      DArray<double> db, dx((size_t)std::max(std::max(m.ncols, m.nrows), 1));
+      db.upload(b, (size_t)m.nrows);
+      h->ams->apply(db.data(), dx.data());
+      dx.download(x, (size_t)m.nrows);
+      gs_free_check();
+      return HDA_OK;
+   }
    if (h->schwarz)
    { // one application of the Schwarz preconditioner from a zero guess
       const DCsr    &m = h->A->get();
@@ -1119,6 +1194,11 @@ static int run_krylov(int kind, hda_csr_t A, hda_amg_t amg, const hda_krylov_par
    if (amg && amg->mgr)
       M = [amg, &m](const double *r, double *z, int slot) {
          amg->mgr->solve(r, z, true);
+         if (slot >= 0) dot(m.nrows, r, z, slot);
+      };
+   else if (amg && amg->ams)
+      M = [amg, &m](const double *r, double *z, int slot) {
+         amg->ams->apply(r, z);
          if (slot >= 0) dot(m.nrows, r, z, slot);
       };
    else if (amg && amg->schwarz)

@@ -48,7 +48,7 @@ struct hypre_IJMatrix_struct {
    bool assemble_csr(const long long *indptr, const long long *cols, const double *data);
 };
 
-enum hda_solver_kind { HDA_SOLVER_PCG = 1, HDA_SOLVER_GMRES = 2, HDA_SOLVER_AMG = 3, HDA_SOLVER_ILU = 4, HDA_SOLVER_FGMRES = 5, HDA_SOLVER_BICGSTAB = 6, HDA_SOLVER_MGR = 7, HDA_SOLVER_SCHWARZ = 8 };
+enum hda_solver_kind { HDA_SOLVER_PCG = 1, HDA_SOLVER_GMRES = 2, HDA_SOLVER_AMG = 3, HDA_SOLVER_ILU = 4, HDA_SOLVER_FGMRES = 5, HDA_SOLVER_BICGSTAB = 6, HDA_SOLVER_MGR = 7, HDA_SOLVER_SCHWARZ = 8, HDA_SOLVER_AMS = 9 };
 
 namespace hda {
 // addresses of the live solver objects THIS library created: an opaque HYPRE_Solver a caller installs with
@@ -87,6 +87,15 @@ struct hypre_Solver_struct {
    int                           sw_variant = 0, sw_overlap = 1, sw_domain_type = 2, sw_num_functions = 1, sw_nonsymm = 0, sw_local_solver = 0,
                                  sw_fill = 0, sw_max_iter = 1, sw_print_level = 0, sw_logging = 0;
    double                        sw_weight = 1.0, sw_tol = 0.0;
+   // HYPRE_AMS* handle: what the setters recorded (defaults: the reference's GPU build, src/internal/ams.c:15-22), checked at Setup; G and
+   // the coordinate vectors are borrowed, as in hypre
+   std::unique_ptr<hda::Ams>     ams;
+   hda::AmsParams                amsp;
+   hda::AmsAmgOptions            ams_alpha, ams_beta;
+   int                           ams_print_level = 0, ams_proj_freq = 5; // (proj_freq and omega act in the singular case / with relax_type 2 only)
+   double                        ams_omega = 1.0;
+   HYPRE_ParCSRMatrix            ams_G = nullptr;
+   HYPRE_ParVector               ams_xyz[3] = {nullptr, nullptr, nullptr};
    // HYPRE_MGR* handle: what the setters recorded (hypre's per-level arrays, copied), built at Setup
    std::unique_ptr<hda::Mgr>     mgr;
    int                           mgr_block_size = 0, mgr_levels = 0, mgr_max_iter = 1, mgr_cycle = 1, mgr_frelax_cycle = 1, mgr_gsmooth_cycle = 1;

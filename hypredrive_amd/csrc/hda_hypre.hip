@@ -63,6 +63,18 @@ extern "C" HYPRE_Int HYPRE_ClearAllErrors(void)
    return 0;
 }
 extern "C" HYPRE_Int HYPRE_CheckError(HYPRE_Int ierr, HYPRE_Int code) { return ierr & code; }
+// hypre's contract: descr has room for 128 characters.  The text of the last failed call of this rank when there is one (it names
+// what was refused), else the meaning of the bits of ierr
+extern "C" HYPRE_Int HYPRE_DescribeError(HYPRE_Int ierr, char *descr)
+{
+   if (!descr) return hypre_set_error(HYPRE_ERROR_ARG, "HYPRE_DescribeError: null buffer");
+   std::string t = g_herr;
+   if (t.empty())
+      t = !ierr ? "[No error] " : std::string(ierr & HYPRE_ERROR_GENERIC ? "[Generic error] " : "") + (ierr & HYPRE_ERROR_MEMORY ? "[Memory error] " : "") +
+                                     (ierr & HYPRE_ERROR_ARG ? "[Error in argument] " : "") + (ierr & HYPRE_ERROR_CONV ? "[Method did not converge] " : "");
+   snprintf(descr, 128, "%s", t.c_str());
+   return 0;
+}
 
 // --------------------------------------------------------------------- vectors
 
@@ -1596,6 +1608,134 @@ extern "C" HYPRE_Int HYPRE_SchwarzSolve(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HY
    HY_CATCH
 }
 
+// ------------------------------------------------------------------------ AMS
+// HYPRE_AMS* as driven by hypredrv_AMSCreate / hypredrv_AMSSetOperators (reference src/internal/ams.c:78-133).  Built (hda_ams.hip,
+// DESIGN section 18): the multiplicative cycles 1, 3, 5, 7 with l1-Jacobi smoothing on one rank; ams_refusal names the rest.
+
+static AmsParams ams_params_of(const hypre_Solver_struct *s)
+{
+   AmsParams p = s->amsp;
+   p.alpha     = ams_subspace_amg(s->ams_alpha, p.dimension);
+   p.beta      = ams_subspace_amg(s->ams_beta, 1);
+   return p;
+}
+extern "C" HYPRE_Int HYPRE_AMSCreate(HYPRE_Solver *solver)
+{
+   if (!solver) return hypre_set_error(HYPRE_ERROR_ARG, "HYPRE_AMSCreate: null output");
+   auto *s = new hypre_Solver_struct();
+   s->kind = HDA_SOLVER_AMS;
+   *solver = s;
+   return 0;
+}
+// (precon.c:138-154 calls this for whatever handle its table holds: NULL is fine, a handle of another kind is not an AMS handle)
+extern "C" HYPRE_Int HYPRE_AMSDestroy(HYPRE_Solver s)
+{
+   if (!s) return 0;
+   if (!is_live_solver(s) || s->kind != HDA_SOLVER_AMS) return hypre_set_error(HYPRE_ERROR_ARG, "HYPRE_AMSDestroy: not an AMS handle");
+   return HYPRE_BoomerAMGDestroy(s);
+}
+HY_SETTER(HYPRE_AMSSetDimension, HYPRE_Int, s->amsp.dimension = v)
+HY_SETTER(HYPRE_AMSSetMaxIter, HYPRE_Int, s->amsp.max_iter = v)
+HY_SETTER(HYPRE_AMSSetTol, HYPRE_Real, s->amsp.tolerance = v)
+HY_SETTER(HYPRE_AMSSetCycleType, HYPRE_Int, s->amsp.cycle_type = v)
+HY_SETTER(HYPRE_AMSSetPrintLevel, HYPRE_Int, s->ams_print_level = v)
+HY_SETTER(HYPRE_AMSSetAlphaAMGCoarseRelaxType, HYPRE_Int, s->ams_alpha.coarse_relax_type = v)
+HY_SETTER(HYPRE_AMSSetBetaAMGCoarseRelaxType, HYPRE_Int, s->ams_beta.coarse_relax_type = v)
+HY_SETTER(HYPRE_AMSSetProjectionFrequency, HYPRE_Int, s->ams_proj_freq = v) // (the singular case only)
+HY_SETTER(HYPRE_AMSSetDiscreteGradient, HYPRE_ParCSRMatrix, s->ams_G = v)
+extern "C" HYPRE_Int HYPRE_AMSSetSmoothingOptions(HYPRE_Solver s, HYPRE_Int relax_type, HYPRE_Int relax_times, HYPRE_Real relax_weight, HYPRE_Real omega)
+{
+   if (!s) return hypre_set_error(HYPRE_ERROR_ARG, "HYPRE_AMSSetSmoothingOptions: null solver");
+   s->amsp.relax_type = relax_type; s->amsp.relax_times = relax_times; s->amsp.relax_weight = relax_weight;
+   s->ams_omega = omega; // (acts with relax_type 2 only)
+   return 0;
+}
+static HYPRE_Int ams_set_amg(HYPRE_Solver s, AmsAmgOptions hypre_Solver_struct::*which, const char *fn, HYPRE_Int coarsen_type, HYPRE_Int agg_levels,
+                             HYPRE_Int relax_type, HYPRE_Real theta, HYPRE_Int interp_type, HYPRE_Int pmax)
+{
+   if (!s) return hypre_set_error(HYPRE_ERROR_ARG, std::string(fn) + ": null solver");
+   AmsAmgOptions &o = s->*which;
+   o.coarsen_type = coarsen_type; o.agg_levels = agg_levels; o.relax_type = relax_type; o.strength_threshold = theta;
+   o.interp_type = interp_type; o.pmax = pmax;
+   return 0;
+}
+extern "C" HYPRE_Int HYPRE_AMSSetAlphaAMGOptions(HYPRE_Solver s, HYPRE_Int coarsen_type, HYPRE_Int agg_levels, HYPRE_Int relax_type,
+                                                 HYPRE_Real strength_threshold, HYPRE_Int interp_type, HYPRE_Int Pmax)
+{
+   return ams_set_amg(s, &hypre_Solver_struct::ams_alpha, "HYPRE_AMSSetAlphaAMGOptions", coarsen_type, agg_levels, relax_type, strength_threshold, interp_type, Pmax);
+}
+extern "C" HYPRE_Int HYPRE_AMSSetBetaAMGOptions(HYPRE_Solver s, HYPRE_Int coarsen_type, HYPRE_Int agg_levels, HYPRE_Int relax_type,
+                                                HYPRE_Real strength_threshold, HYPRE_Int interp_type, HYPRE_Int Pmax)
+{
+   return ams_set_amg(s, &hypre_Solver_struct::ams_beta, "HYPRE_AMSSetBetaAMGOptions", coarsen_type, agg_levels, relax_type, strength_threshold, interp_type, Pmax);
+}
+extern "C" HYPRE_Int HYPRE_AMSSetCoordinateVectors(HYPRE_Solver s, HYPRE_ParVector x, HYPRE_ParVector y, HYPRE_ParVector z)
+{
+   if (!s) return hypre_set_error(HYPRE_ERROR_ARG, "HYPRE_AMSSetCoordinateVectors: null solver");
+   s->ams_xyz[0] = x; s->ams_xyz[1] = y; s->ams_xyz[2] = z;
+   return 0;
+}
+
+extern "C" HYPRE_Int HYPRE_AMSSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector, HYPRE_ParVector)
+{
+   HY_TRY
+   HDA_REQUIRE(s && is_live_solver(s) && s->kind == HDA_SOLVER_AMS, "AMSSetup: not an AMS handle");
+   const AmsParams   p   = ams_params_of(s);
+   const std::string why = ams_refusal(p);
+   if (!why.empty()) throw Error(why);
+   HDA_REQUIRE(Comm::world().size == 1, "AMS: a world of more than one rank is not implemented (row partitions of G and Pi are not built); one rank is");
+   if (!have_device()) throw Error("no HIP device visible: the MI355X solve path has no CPU fallback");
+   HDA_REQUIRE(A && A->assembled, "AMSSetup needs an assembled matrix");
+   HYPRE_ParCSRMatrix G = s->ams_G;
+   if (!G || !s->ams_xyz[0] || !s->ams_xyz[1] || (p.dimension == 3 && !s->ams_xyz[2]))
+      throw Error("AMS setup requires a discrete gradient matrix and coordinate vectors, but they were not provided");
+   HDA_REQUIRE(G->assembled, "AMSSetup needs an assembled discrete gradient");
+   HDA_REQUIRE(G->A.nrows == A->A.nrows, "AMS: the discrete gradient needs one row per row of the operator");
+   HDA_REQUIRE(G->ghost_gids.empty(), "AMS: the discrete gradient names columns outside its column range");
+   const double *c[3] = {nullptr, nullptr, nullptr};
+   for (int k = 0; k < p.dimension; k++)
+   {
+      HYPRE_ParVector v = s->ams_xyz[k];
+      HDA_REQUIRE(v->nloc == G->A.ncols, "AMS: a coordinate vector needs one entry per column of the discrete gradient");
+      v->ensure_device();
+      c[k] = v->data();
+   }
+   s->ams = std::make_unique<Ams>();
+   s->ams->setup(A->A, G->A, c, p);
+   Ams &S = *s->ams;
+   if (s->ams_print_level >= 1)
+      printf("AMS (cycle %d, dimension %d): n_e %d, n_v %d, nnz(Pi) %d, A_G %d rows / %d levels, A_Pi %d rows / %d levels, repaired rows %d + %d\n",
+             p.cycle_type, p.dimension, S.n_e, S.n_v, S.pi().nnz, S.a_g().nrows, S.b_g().num_levels(), S.a_pi().nrows, S.b_pi().num_levels(),
+             S.fixed_rows[0], S.fixed_rows[1]);
+   hda_register_precond_veclen((size_t)std::max(A->A.ncols, A->A.nrows));
+   HY_CATCH
+}
+
+extern "C" HYPRE_Int HYPRE_AMSSolve(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
+{
+   HY_NEED_DEVICE;
+   HY_TRY
+   HDA_REQUIRE(s && is_live_solver(s) && s->kind == HDA_SOLVER_AMS, "AMSSolve: not an AMS handle");
+   HDA_REQUIRE(s->ams, "AMSSolve before AMSSetup");
+   HDA_REQUIRE(A && A->assembled && b && x, "AMSSolve needs an assembled matrix and two vectors");
+   HDA_REQUIRE(A->A.nrows == s->ams->n_e && b->nloc == A->A.nrows && x->nloc == A->A.nrows, "AMSSolve: the system is not the size of the one set up");
+   x->ensure_device();
+   const int     n = A->A.nrows;
+   PrecondHints &h = precond_hints();
+   if (h.zero_guess) s->ams->apply(b->data(), x->data());
+   else
+   { // the cycle is a stationary iteration: from x it gives x + M (b - A x)
+      const size_t len = (size_t)std::max(std::max(A->A.ncols, n), 1);
+      if (s->ilu_r.size() < len) s->ilu_r.alloc(len);
+      if (s->ilu_c.size() < len) s->ilu_c.alloc(len);
+      residual(A->A, x->data(), b->data(), s->ilu_r.data());
+      s->ams->apply(s->ilu_r.data(), s->ilu_c.data());
+      axpy(n, 1.0, s->ilu_c.data(), x->data());
+   }
+   s->amg_iters = std::max(s->amsp.max_iter, 1);
+   HY_CATCH
+}
+
 // ------------------------------------------------------------------------ MGR
 // HYPRE_MGR* as driven by hypredrv_MGRCreate (reference src/internal/mgr.c:3782-3808 base settings, per-level
 // arrays after :3820).  hypre's calling convention is kept: C points of every reduction level by dof label
@@ -1902,7 +2042,6 @@ HY_REFUSED(HYPRE_ParCSRGMRESSetRefSolution, (HYPRE_Solver, HYPRE_ParVector), "er
 #define HY_FOREIGN_DESTROY(fn, what) \
    extern "C" HYPRE_Int fn(HYPRE_Solver s) { return s ? hypre_set_error(HYPRE_ERROR_ARG, #fn ": " what " handles are never created by this library") : 0; }
 HY_FOREIGN_DESTROY(HYPRE_FSAIDestroy, "FSAI")
-HY_FOREIGN_DESTROY(HYPRE_AMSDestroy, "AMS")
 HY_FOREIGN_DESTROY(HYPRE_ADSDestroy, "ADS")
 #undef HY_FOREIGN_DESTROY
 

@@ -169,6 +169,11 @@ struct hypredrv_struct {
    bool           owns_M = false; // the preconditioning matrix was read from linear_system.precmat_filename
    HYPRE_IJVector vec_b = nullptr, vec_x = nullptr, vec_x0 = nullptr, vec_xref = nullptr;
    bool           owns_A = false, owns_b = false, owns_x = false, owns_x0 = false;
+   // AMS operators (HYPREDRV_LinearSystemSetDiscreteGradient / SetCoordinates; reference src/HYPREDRV.c:2023-2094): borrowed in
+   // library mode, owned otherwise
+   HYPRE_IJMatrix mat_G = nullptr;
+   HYPRE_IJVector vec_coord[3] = {nullptr, nullptr, nullptr};
+   bool           owns_G = false, owns_coord = false;
    HYPRE_Solver   solver = nullptr, precon = nullptr;
    bool           precon_is_setup = false;
    PreconCookie   cookie{nullptr};
@@ -384,6 +389,27 @@ static void destroy_system(hypredrv_struct *h)
    h->vec_b = h->vec_x = h->vec_x0 = nullptr;
    h->owns_A = h->owns_b = h->owns_x = h->owns_x0 = false;
 }
+// an AMS preconditioner borrows G and the coordinate vectors from Create to Setup: it is told whenever they change
+static void ams_hand_over(hypredrv_struct *h)
+{
+   if (!h->precon || h->precon->kind != HDA_SOLVER_AMS) return;
+   HYPRE_AMSSetDiscreteGradient(h->precon, h->mat_G);
+   HYPRE_AMSSetCoordinateVectors(h->precon, h->vec_coord[0], h->vec_coord[1], h->vec_coord[2]);
+}
+static void destroy_ams_operators(hypredrv_struct *h)
+{
+   if (h->owns_G && h->mat_G) HYPRE_IJMatrixDestroy(h->mat_G);
+   if (h->owns_coord)
+      for (int i = 0; i < 3; i++)
+      {
+         HYPRE_IJVector v = h->vec_coord[i];
+         if (v && (i < 1 || v != h->vec_coord[0]) && (i < 2 || v != h->vec_coord[1])) HYPRE_IJVectorDestroy(v);
+      }
+   h->mat_G = nullptr;
+   h->vec_coord[0] = h->vec_coord[1] = h->vec_coord[2] = nullptr;
+   h->owns_G = h->owns_coord = false;
+   ams_hand_over(h);
+}
 
 extern "C" uint32_t HYPREDRV_Destroy(HYPREDRV_t *hp)
 {
@@ -393,6 +419,8 @@ extern "C" uint32_t HYPREDRV_Destroy(HYPREDRV_t *hp)
    if (h->precon) HYPRE_BoomerAMGDestroy(h->precon);
    for (HYPRE_Solver a : h->precon_aux) HYPRE_BoomerAMGDestroy(a);
    h->precon_aux.clear();
+   h->precon = nullptr;
+   destroy_ams_operators(h);
    destroy_system(h);
    delete h;
    *hp = nullptr;
@@ -1136,9 +1164,35 @@ extern "C" uint32_t HYPREDRV_LinearSystemPrint(HYPREDRV_t h)
    {                                                                                    \
       return err_set(HYPREDRV_ERROR_UNSUPPORTED_AMD, what " is outside the MI355X AMG-Krylov path of this build"); \
    }
-UNSUPPORTED(HYPREDRV_LinearSystemSetDiscreteGradient(HYPREDRV_t, HYPRE_Matrix), "AMS/ADS discrete gradient")
 UNSUPPORTED(HYPREDRV_LinearSystemSetDiscreteCurl(HYPREDRV_t, HYPRE_Matrix), "ADS discrete curl")
-UNSUPPORTED(HYPREDRV_LinearSystemSetCoordinates(HYPREDRV_t, HYPRE_Vector, HYPRE_Vector, HYPRE_Vector), "AMS/ADS coordinates")
+// AMS operators (reference src/HYPREDRV.c:2023-2094): library mode borrows the handles; otherwise they are owned, an owned handle that
+// is replaced is destroyed, NULL clears
+extern "C" uint32_t HYPREDRV_LinearSystemSetDiscreteGradient(HYPREDRV_t h, HYPRE_Matrix G)
+{
+   CHECK_INIT_OBJ(h);
+   if (h->mat_G && h->owns_G && h->mat_G != G) HYPRE_IJMatrixDestroy(h->mat_G);
+   h->mat_G  = G;
+   h->owns_G = !h->lib_mode && G != nullptr;
+   ams_hand_over(h);
+   return g_err;
+}
+extern "C" uint32_t HYPREDRV_LinearSystemSetCoordinates(HYPREDRV_t h, HYPRE_Vector x, HYPRE_Vector y, HYPRE_Vector z)
+{
+   CHECK_INIT_OBJ(h);
+   HYPRE_IJVector nv[3] = {x, y, z};
+   if (h->owns_coord)
+      for (int i = 0; i < 3; i++)
+      {
+         HYPRE_IJVector old = h->vec_coord[i];
+         bool           dup = false; // (the same old handle in two slots is destroyed once)
+         for (int j = 0; j < i; j++) dup = dup || h->vec_coord[j] == old;
+         if (old && !dup && old != nv[0] && old != nv[1] && old != nv[2]) HYPRE_IJVectorDestroy(old);
+      }
+   for (int i = 0; i < 3; i++) h->vec_coord[i] = nv[i];
+   h->owns_coord = !h->lib_mode && x != nullptr;
+   ams_hand_over(h);
+   return g_err;
+}
 // degree-of-freedom maps (reference src/HYPREDRV.c:2680-2724): here they feed BoomerAMG's dof_func when
 // systems AMG is selected (coarsening.num_functions > 1, reference src/internal/amg.c:792-862)
 extern "C" uint32_t HYPREDRV_LinearSystemSetDofmap(HYPREDRV_t h, int size, const int *dofmap)
@@ -1587,8 +1641,18 @@ static const SolverOps &solver_ops(const HYPRE_Solver s)
 static HYPRE_Int PreconSetupDispatch(HYPRE_Solver cookie, HYPRE_Matrix A, HYPRE_Vector b, HYPRE_Vector x)
 {
    hypredrv_struct *h = ((PreconCookie *)(void *)cookie)->self;
+   if (h->precon->kind == HDA_SOLVER_AMS)
+   { // hypredrv_PreconSetupOperatorGuard (reference src/internal/precon.c:675-702)
+      if (!h->mat_G || !h->vec_coord[0] || !h->vec_coord[1] || !h->vec_coord[2])
+      {
+         err_set(ERR_MISSING_PRECON, "AMS setup requires a discrete gradient matrix and coordinate vectors, but they were not provided");
+         return 1;
+      }
+      ams_hand_over(h);
+   }
    annotate(h, "prec", true);
    HYPRE_Int ierr = (h->precon->kind == HDA_SOLVER_ILU)   ? HYPRE_ILUSetup(h->precon, A, b, x)
+                    : (h->precon->kind == HDA_SOLVER_AMS) ? HYPRE_AMSSetup(h->precon, A, b, x)
                     : (h->precon->kind == HDA_SOLVER_SCHWARZ) ? HYPRE_SchwarzSetup(h->precon, A, b, x)
                     : (h->precon->kind == HDA_SOLVER_MGR) ? HYPRE_MGRSetup(h->precon, A, b, x)
                                                           : HYPRE_BoomerAMGSetup(h->precon, A, b, x);
@@ -1602,6 +1666,7 @@ static HYPRE_Int PreconSolveDispatch(HYPRE_Solver cookie, HYPRE_Matrix A, HYPRE_
 {
    hypredrv_struct *h = ((PreconCookie *)(void *)cookie)->self;
    return (h->precon->kind == HDA_SOLVER_ILU)   ? HYPRE_ILUSolve(h->precon, A, b, x)
+          : (h->precon->kind == HDA_SOLVER_AMS) ? HYPRE_AMSSolve(h->precon, A, b, x)
           : (h->precon->kind == HDA_SOLVER_SCHWARZ) ? HYPRE_SchwarzSolve(h->precon, A, b, x)
           : (h->precon->kind == HDA_SOLVER_MGR) ? HYPRE_MGRSolve(h->precon, A, b, x)
                                                 : HYPRE_BoomerAMGSolve(h->precon, A, b, x);
@@ -1648,6 +1713,27 @@ static void schwarz_create(const SchwarzArgs &a, HYPRE_Solver *out)
    HYPRE_SchwarzSetTol(p, a.tolerance);
    HYPRE_SchwarzSetPrintLevel(p, a.print_level);
    HYPRE_SchwarzSetLogging(p, a.logging);
+   *out = p;
+}
+
+// hypredrv_AMSCreate (reference src/internal/ams.c:78-102): same setter sequence
+static void ams_create(const AmsArgs &a, HYPRE_Solver *out)
+{
+   HYPRE_Solver p = nullptr;
+   HYPRE_AMSCreate(&p);
+   HYPRE_AMSSetDimension(p, a.dimension);
+   HYPRE_AMSSetMaxIter(p, a.max_iter);
+   HYPRE_AMSSetTol(p, a.tolerance);
+   HYPRE_AMSSetCycleType(p, a.cycle_type);
+   HYPRE_AMSSetPrintLevel(p, a.print_level);
+   HYPRE_AMSSetSmoothingOptions(p, a.relax_type, a.relax_times, a.relax_weight, a.omega);
+   HYPRE_AMSSetAlphaAMGOptions(p, a.alpha_coarsen_type, a.alpha_agg_levels, a.alpha_relax_type, a.alpha_strength_threshold, a.alpha_interp_type,
+                               a.alpha_Pmax);
+   HYPRE_AMSSetAlphaAMGCoarseRelaxType(p, a.alpha_coarse_relax_type);
+   HYPRE_AMSSetBetaAMGOptions(p, a.beta_coarsen_type, a.beta_agg_levels, a.beta_relax_type, a.beta_strength_threshold, a.beta_interp_type,
+                              a.beta_Pmax);
+   HYPRE_AMSSetBetaAMGCoarseRelaxType(p, a.beta_coarse_relax_type);
+   HYPRE_AMSSetProjectionFrequency(p, a.proj_freq);
    *out = p;
 }
 
@@ -1958,9 +2044,26 @@ extern "C" uint32_t HYPREDRV_PreconCreate(HYPREDRV_t h)
       return g_err;
    }
    if (p.method == 1) return mgr_create(h, p.mgr);
+   if (p.method == 4)
+   { // as Schwarz: every value parses, what is not built is refused here by the name of its key
+      const AmsArgs &a = p.ams;
+      AmsParams      q;
+      q.dimension = a.dimension; q.max_iter = a.max_iter; q.cycle_type = a.cycle_type; q.relax_type = a.relax_type;
+      q.relax_times = a.relax_times; q.tolerance = a.tolerance; q.relax_weight = a.relax_weight;
+      q.alpha.agg_num_levels = a.alpha_agg_levels;
+      const std::string why  = ams_refusal(q);
+      if (!why.empty()) return err_set(ERR_INVALID_PRECON | HYPREDRV_ERROR_UNSUPPORTED_AMD, why);
+      if (Comm::world().size > 1)
+         return err_set(ERR_INVALID_PRECON | HYPREDRV_ERROR_UNSUPPORTED_AMD,
+                        "AMS: a world of more than one rank is not implemented (row partitions of G and Pi are not built); one rank is");
+      ams_create(a, &h->precon);
+      ams_hand_over(h);
+      consume_hypre_errors();
+      return g_err;
+   }
    if (p.method != 0)
       return err_set(ERR_INVALID_PRECON | HYPREDRV_ERROR_UNSUPPORTED_AMD,
-                     "preconditioner '" + p.method_name + "' is not implemented on MI355X yet (BoomerAMG, ILU, MGR and Schwarz only)");
+                     "preconditioner '" + p.method_name + "' is not implemented on MI355X yet (BoomerAMG, ILU, MGR, Schwarz and AMS only)");
    amg_create(p.amg, &h->precon);
    // hypredrv_AMGSetDofFunc (reference src/internal/amg.c:792-862): the dofmap names the function of
    // every local unknown when its labels fit [0, num_functions); otherwise hypre's interleaved default
@@ -2339,6 +2442,7 @@ extern "C" uint32_t HYPREDRV_PreconApply(HYPREDRV_t h, HYPRE_Vector b, HYPRE_Vec
    if (!h->precon || !h->precon_is_setup) return err_set(ERR_INVALID_PRECON, "PreconApply requires a set-up preconditioner");
    if (h->precon->kind == HDA_SOLVER_ILU) HYPRE_ILUSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
    else if (h->precon->kind == HDA_SOLVER_SCHWARZ) HYPRE_SchwarzSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
+   else if (h->precon->kind == HDA_SOLVER_AMS) HYPRE_AMSSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
    else if (h->precon->kind == HDA_SOLVER_MGR) HYPRE_MGRSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
    else HYPRE_BoomerAMGSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
    consume_hypre_errors();

@@ -459,6 +459,25 @@ static void schwarz_fields(Ctx &c, YNode &sec, SchwarzArgs &a)
                  {"ilut_droptol", nullptr, &a.ilut_droptol, nullptr}, {"tolerance", nullptr, &a.tolerance, nullptr}});
 }
 
+// AMS_FIELDS (reference src/internal/ams.c:37-63): 24 keys, numbers only (keys arrive in lower case: alpha_Pmax is alpha_pmax
+// here).  Every value parses; what is not built is refused at HYPREDRV_PreconCreate.
+static void ams_fields(Ctx &c, YNode &sec, AmsArgs &a)
+{
+   apply_fields(c, sec,
+                {{"dimension", &a.dimension, nullptr, nullptr}, {"max_iter", &a.max_iter, nullptr, nullptr}, {"print_level", &a.print_level, nullptr, nullptr},
+                 {"cycle_type", &a.cycle_type, nullptr, nullptr}, {"tolerance", nullptr, &a.tolerance, nullptr},
+                 {"relax_type", &a.relax_type, nullptr, nullptr}, {"relax_times", &a.relax_times, nullptr, nullptr},
+                 {"relax_weight", nullptr, &a.relax_weight, nullptr}, {"omega", nullptr, &a.omega, nullptr}, {"proj_freq", &a.proj_freq, nullptr, nullptr},
+                 {"alpha_coarsen_type", &a.alpha_coarsen_type, nullptr, nullptr}, {"alpha_agg_levels", &a.alpha_agg_levels, nullptr, nullptr},
+                 {"alpha_relax_type", &a.alpha_relax_type, nullptr, nullptr}, {"alpha_strength_threshold", nullptr, &a.alpha_strength_threshold, nullptr},
+                 {"alpha_interp_type", &a.alpha_interp_type, nullptr, nullptr}, {"alpha_pmax", &a.alpha_Pmax, nullptr, nullptr},
+                 {"alpha_coarse_relax_type", &a.alpha_coarse_relax_type, nullptr, nullptr},
+                 {"beta_coarsen_type", &a.beta_coarsen_type, nullptr, nullptr}, {"beta_agg_levels", &a.beta_agg_levels, nullptr, nullptr},
+                 {"beta_relax_type", &a.beta_relax_type, nullptr, nullptr}, {"beta_strength_threshold", nullptr, &a.beta_strength_threshold, nullptr},
+                 {"beta_interp_type", &a.beta_interp_type, nullptr, nullptr}, {"beta_pmax", &a.beta_Pmax, nullptr, nullptr},
+                 {"beta_coarse_relax_type", &a.beta_coarse_relax_type, nullptr, nullptr}});
+}
+
 // mgr block (reference src/internal/mgr.c:1736-1870; value maps :1553-1721)
 static const StrMap kMgrInterp = {{"injection", 0}, {"l1-jacobi", 1}, {"jacobi", 2}, {"classical-mod", 3}, {"approx-inv", 4}, {"blk-jacobi", 12},
                                   {"blk-rowlump", 13}, {"blk-rowsum", 13}, {"blk-absrowsum", 14}};
@@ -962,6 +981,7 @@ static void parse_precon_body(Ctx &c, YNode &node, std::vector<PreconArgs> &vari
             else if (p.method == 2) ilu_fields(c, *item, v.ilu);
             else if (p.method == 1) mgr_fields(c, *item, v.mgr);
             else if (p.method == 6) schwarz_fields(c, *item, v.schwarz);
+            else if (p.method == 4) ams_fields(c, *item, v.ams);
             variants.push_back(v);
          }
       }
@@ -971,6 +991,7 @@ static void parse_precon_body(Ctx &c, YNode &node, std::vector<PreconArgs> &vari
          else if (p.method == 2) ilu_fields(c, *ch, p.ilu);
          else if (p.method == 1) mgr_fields(c, *ch, p.mgr);
          else if (p.method == 6) schwarz_fields(c, *ch, p.schwarz);
+         else if (p.method == 4) ams_fields(c, *ch, p.ams);
          variants.push_back(p);
       }
    }

@@ -78,6 +78,26 @@ struct SchwarzArgs { // Schwarz_args, defaults of src/internal/schwarz.c:20-34 (
           ilut_max_nnz_row = 1000, max_iter = 1, print_level = 0, logging = 0;
    double relax_weight = 1.0, ilut_droptol = 1.0e-2, tolerance = 0.0;
 };
+struct AmsArgs { // AMS_args, defaults of src/internal/ams.c:15-22 (GPU build), :37-63; HYPREDRV_AMD_DEFAULTS=cpu: those of a CPU build
+   int    dimension = 3, max_iter = 1, print_level = 0, cycle_type = 1, relax_type = 1, relax_times = 1, proj_freq = 5;
+   double tolerance = 0.0, relax_weight = 1.0, omega = 1.0;
+   int    alpha_coarsen_type = 8, alpha_agg_levels = 1, alpha_relax_type = 18, alpha_interp_type = 6, alpha_Pmax = 4, alpha_coarse_relax_type = 18;
+   int    beta_coarsen_type = 8, beta_agg_levels = 1, beta_relax_type = 18, beta_interp_type = 6, beta_Pmax = 4, beta_coarse_relax_type = 18;
+   double alpha_strength_threshold = 0.25, beta_strength_threshold = 0.25;
+   AmsArgs()
+   {
+      const char *e = getenv("HYPREDRV_AMD_DEFAULTS");
+      if (e && !strcmp(e, "cpu"))
+      {
+         relax_type         = 2;
+         alpha_coarsen_type = beta_coarsen_type = 10;
+         alpha_relax_type = beta_relax_type = 3;
+         alpha_interp_type = beta_interp_type = 0;
+         alpha_Pmax = beta_Pmax = 0;
+         alpha_coarse_relax_type = beta_coarse_relax_type = 8;
+      }
+   }
+};
 struct AmgArgs { // AMG_args, GPU-branch defaults of src/internal/amg.c:120-238
    int    max_iter = 1, print_level = 0;
    double tolerance = 0.0;
@@ -150,6 +170,7 @@ struct PreconArgs {
    IluArgs     ilu;
    MgrArgs     mgr;
    SchwarzArgs schwarz;
+   AmsArgs     ams;
 };
 // preconditioner.reuse (reference src/internal/precon_reuse.c:2280-2567): the static policy
 struct ReuseArgs {

@@ -66,6 +66,9 @@ def lib():
         "HYPREDRV_AMD_CommFinalize": [],
         "HYPREDRV_AMD_LinearSystemSetLaplacian7pt": [vp, ip, ip, dp],
         "HYPREDRV_AMD_LinearSystemSetEmptyBlock": [vp, C.c_longlong],
+        "HYPREDRV_LinearSystemSetMatrix": [vp, vp], "HYPREDRV_LinearSystemSetRHS": [vp, vp],
+        "HYPREDRV_LinearSystemSetDiscreteGradient": [vp, vp], "HYPREDRV_LinearSystemSetDiscreteCurl": [vp, vp],
+        "HYPREDRV_LinearSystemSetCoordinates": [vp, vp, vp, vp],
         "HYPREDRV_LinearSystemSetDofmap": [vp, C.c_int, ip],
         "HYPREDRV_LinearSystemSetInterleavedDofmap": [vp, C.c_int, C.c_int],
         "HYPREDRV_LinearSystemSetContiguousDofmap": [vp, C.c_int, C.c_int],
@@ -89,6 +92,52 @@ def lib():
     L.HYPREDRV_AMD_LastErrorMessage.restype = C.c_char_p
     _configured = True
     return L
+
+
+def ij_matrix(m, ilower=0, jlower=0):
+    """A scipy matrix as an assembled HYPRE_IJMatrix (a handle, c_void_p) whose rows start at ilower and whose columns start at jlower:
+    the column range of a rectangular matrix is its own."""
+    L = lib()
+    m = m.tocsr()
+    ll = C.POINTER(C.c_longlong)
+    L.HYPRE_IJMatrixCreate.argtypes = [C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, C.POINTER(C.c_void_p)]
+    L.HYPRE_IJMatrixSetObjectType.argtypes = [C.c_void_p, C.c_int]
+    L.HYPRE_IJMatrixInitialize.argtypes = L.HYPRE_IJMatrixAssemble.argtypes = L.HYPRE_IJMatrixDestroy.argtypes = [C.c_void_p]
+    L.HYPRE_IJMatrixSetValues.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), ll, ll, C.POINTER(C.c_double)]
+    h = C.c_void_p()
+    n, nc = m.shape
+    ok = L.HYPRE_IJMatrixCreate(MPI_COMM_WORLD, ilower, ilower + n - 1, jlower, jlower + nc - 1, C.byref(h)) == 0
+    ok = ok and L.HYPRE_IJMatrixSetObjectType(h, 5555) == 0 and L.HYPRE_IJMatrixInitialize(h) == 0
+    sizes = np.ascontiguousarray(np.diff(m.indptr), dtype=np.int32)
+    rows = np.arange(ilower, ilower + n, dtype=np.int64)
+    cols = np.ascontiguousarray(m.indices, dtype=np.int64) + jlower
+    vals = np.ascontiguousarray(m.data, dtype=np.float64)
+    ok = ok and L.HYPRE_IJMatrixSetValues(h, n, sizes.ctypes.data_as(C.POINTER(C.c_int)), rows.ctypes.data_as(ll), cols.ctypes.data_as(ll),
+                                          vals.ctypes.data_as(C.POINTER(C.c_double))) == 0
+    ok = ok and L.HYPRE_IJMatrixAssemble(h) == 0
+    if not ok:
+        raise LibraryError("building an IJ matrix failed")
+    return h
+
+
+def ij_vector(values, jlower=0):
+    """A numpy vector as an assembled HYPRE_IJVector (a handle, c_void_p) whose entries start at jlower"""
+    L = lib()
+    ll = C.POINTER(C.c_longlong)
+    L.HYPRE_IJVectorCreate.argtypes = [C.c_int, C.c_longlong, C.c_longlong, C.POINTER(C.c_void_p)]
+    L.HYPRE_IJVectorSetObjectType.argtypes = [C.c_void_p, C.c_int]
+    L.HYPRE_IJVectorInitialize.argtypes = L.HYPRE_IJVectorAssemble.argtypes = L.HYPRE_IJVectorDestroy.argtypes = [C.c_void_p]
+    L.HYPRE_IJVectorSetValues.argtypes = [C.c_void_p, C.c_int, ll, C.POINTER(C.c_double)]
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    idx = np.arange(jlower, jlower + v.size, dtype=np.int64)
+    h = C.c_void_p()
+    ok = L.HYPRE_IJVectorCreate(MPI_COMM_WORLD, jlower, jlower + v.size - 1, C.byref(h)) == 0
+    ok = ok and L.HYPRE_IJVectorSetObjectType(h, 5555) == 0 and L.HYPRE_IJVectorInitialize(h) == 0
+    ok = ok and L.HYPRE_IJVectorSetValues(h, v.size, idx.ctypes.data_as(ll), v.ctypes.data_as(C.POINTER(C.c_double))) == 0
+    ok = ok and L.HYPRE_IJVectorAssemble(h) == 0
+    if not ok:
+        raise LibraryError("building an IJ vector failed")
+    return h
 
 
 class HypredrvError(LibraryError):
@@ -147,6 +196,21 @@ class Hypredrv:
 
     def set_laplacian7(self, n, P=(1, 1, 1), c=(1.0, 1.0, 1.0)):
         check(lib().HYPREDRV_AMD_LinearSystemSetLaplacian7pt(self.h, (C.c_int * 3)(*n), (C.c_int * 3)(*P), (C.c_double * 3)(*c)))
+
+    def set_matrix(self, A):
+        """an IJ matrix handle (ij_matrix); owned by the object unless it is in library mode"""
+        check(lib().HYPREDRV_LinearSystemSetMatrix(self.h, A))
+
+    def set_rhs(self, b):
+        check(lib().HYPREDRV_LinearSystemSetRHS(self.h, b))
+
+    def set_discrete_gradient(self, G):
+        """the AMS discrete gradient, an IJ matrix handle or None"""
+        check(lib().HYPREDRV_LinearSystemSetDiscreteGradient(self.h, G))
+
+    def set_coordinates(self, x, y, z):
+        """the AMS vertex coordinates, three IJ vector handles (or None)"""
+        check(lib().HYPREDRV_LinearSystemSetCoordinates(self.h, x, y, z))
 
     def finish_system(self):
         check(lib().HYPREDRV_LinearSystemSetInitialGuess(self.h, None))

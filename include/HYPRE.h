@@ -28,6 +28,11 @@ typedef int       HYPRE_Int;
 typedef long long HYPRE_BigInt;
 typedef double    HYPRE_Real;
 typedef double    HYPRE_Complex;
+/* MPI datatypes of the number types above, for drivers that reduce them with MPI themselves (examples/src/C_maxwell/maxwell.c:1120) */
+#define HYPRE_MPI_INT MPI_INT
+#define HYPRE_MPI_BIG_INT MPI_LONG_LONG_INT
+#define HYPRE_MPI_REAL MPI_DOUBLE
+#define HYPRE_MPI_COMPLEX MPI_DOUBLE
 
 typedef enum { HYPRE_MEMORY_UNDEFINED = -1, HYPRE_MEMORY_HOST = 0, HYPRE_MEMORY_DEVICE = 1 } HYPRE_MemoryLocation;
 typedef enum { HYPRE_EXEC_UNDEFINED = -1, HYPRE_EXEC_HOST = 0, HYPRE_EXEC_DEVICE = 1 } HYPRE_ExecutionPolicy;
@@ -60,6 +65,7 @@ HYPRE_Int HYPRE_SetExecutionPolicy(HYPRE_ExecutionPolicy pol);
 HYPRE_Int HYPRE_GetError(void);
 HYPRE_Int HYPRE_ClearAllErrors(void);
 HYPRE_Int HYPRE_CheckError(HYPRE_Int ierr, HYPRE_Int code);
+HYPRE_Int HYPRE_DescribeError(HYPRE_Int ierr, char *descr); /* descr: 128 characters; the text of this rank's last failed call, if any */
 
 /* ---- IJ matrix (examples/src/C_laplacian/laplacian.c:734-914, src/internal/linsys.c:1281-1380) ---- */
 HYPRE_Int HYPRE_IJMatrixCreate(MPI_Comm comm, HYPRE_BigInt ilower, HYPRE_BigInt iupper, HYPRE_BigInt jlower,
@@ -358,6 +364,28 @@ HYPRE_Int HYPRE_BoomerAMGSetInterpVectors(HYPRE_Solver solver, HYPRE_Int num_vec
 HYPRE_Int HYPRE_ParCSRGMRESSetRefSolution(HYPRE_Solver solver, HYPRE_ParVector xref);
 HYPRE_Int HYPRE_FSAIDestroy(HYPRE_Solver solver);
 HYPRE_Int HYPRE_AMSDestroy(HYPRE_Solver solver);
+/* ---- AMS as hypredrv_AMSCreate and hypredrv_AMSSetOperators drive it (src/internal/ams.c:78-133).  Built on one rank: cycle types 1,
+ * 3, 5 and 7, relax_type 1 (l1-Jacobi), dimension 2 or 3, tol 0, no aggressive levels on the vector space (alpha agg_levels 0);
+ * everything else is refused by name at HYPRE_AMSSetup.  omega and the projection frequency are recorded and unused.  G and the
+ * coordinate vectors are borrowed until the solver is destroyed.  HYPRE_AMSDestroy accepts NULL and AMS handles only. */
+HYPRE_Int HYPRE_AMSCreate(HYPRE_Solver *solver);
+HYPRE_Int HYPRE_AMSSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_AMSSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_AMSSetDimension(HYPRE_Solver solver, HYPRE_Int dim);
+HYPRE_Int HYPRE_AMSSetMaxIter(HYPRE_Solver solver, HYPRE_Int max_iter);
+HYPRE_Int HYPRE_AMSSetTol(HYPRE_Solver solver, HYPRE_Real tol);
+HYPRE_Int HYPRE_AMSSetCycleType(HYPRE_Solver solver, HYPRE_Int cycle_type);
+HYPRE_Int HYPRE_AMSSetPrintLevel(HYPRE_Solver solver, HYPRE_Int print_level);
+HYPRE_Int HYPRE_AMSSetSmoothingOptions(HYPRE_Solver solver, HYPRE_Int relax_type, HYPRE_Int relax_times, HYPRE_Real relax_weight, HYPRE_Real omega);
+HYPRE_Int HYPRE_AMSSetAlphaAMGOptions(HYPRE_Solver solver, HYPRE_Int coarsen_type, HYPRE_Int agg_levels, HYPRE_Int relax_type,
+                                      HYPRE_Real strength_threshold, HYPRE_Int interp_type, HYPRE_Int Pmax);
+HYPRE_Int HYPRE_AMSSetAlphaAMGCoarseRelaxType(HYPRE_Solver solver, HYPRE_Int coarse_relax_type);
+HYPRE_Int HYPRE_AMSSetBetaAMGOptions(HYPRE_Solver solver, HYPRE_Int coarsen_type, HYPRE_Int agg_levels, HYPRE_Int relax_type,
+                                     HYPRE_Real strength_threshold, HYPRE_Int interp_type, HYPRE_Int Pmax);
+HYPRE_Int HYPRE_AMSSetBetaAMGCoarseRelaxType(HYPRE_Solver solver, HYPRE_Int coarse_relax_type);
+HYPRE_Int HYPRE_AMSSetProjectionFrequency(HYPRE_Solver solver, HYPRE_Int projection_frequency);
+HYPRE_Int HYPRE_AMSSetDiscreteGradient(HYPRE_Solver solver, HYPRE_ParCSRMatrix G);
+HYPRE_Int HYPRE_AMSSetCoordinateVectors(HYPRE_Solver solver, HYPRE_ParVector x, HYPRE_ParVector y, HYPRE_ParVector z);
 HYPRE_Int HYPRE_ADSDestroy(HYPRE_Solver solver);
 /* ---- Schwarz as hypredrv_SchwarzCreate drives it (src/internal/schwarz.c:82-96).  Built: variants 10 (ras-iluk) and 11 (as-iluk) with
  * local solver iluk on one rank (row blocks: HDA_BLOCKS, as for ILU); every other selection is refused by name at Setup.  Destroy

@@ -216,8 +216,23 @@ int hda_schwarz_domains(hda_amg_t h, int *V, int *dom_ptr, int *dom_rows);
 /* info[0..5]: N_ext, nnz of the factors, longest factor row, rows that took the global-memory symbolic path, capacity of the symbolic
  * kernel's LDS table (visited vertices per row), nnz of A; setup_ms (may be NULL): expansion, extraction, symbolic, numeric */
 int hda_schwarz_info(hda_amg_t h, int64_t info[6], double setup_ms[4]);
-/* average device ms of one application (zero guess, vectors resident) of a handle of hda_ilu_create* or hda_schwarz_create */
+/* average device ms of one application (zero guess, vectors resident) of a handle of hda_ilu_create*, hda_schwarz_create or hda_ams_create */
 int hda_precond_time(hda_amg_t h, int reps, double *avg_ms);
+/* "preconditioner: ams" (reference src/internal/ams.c): the auxiliary-space Maxwell preconditioner on one rank.
+ * A is n_e x n_e, G (n_e x n_v) the discrete gradient, c0 / c1 / c2 host vectors of n_v vertex coordinates (c2 is not read when
+ * dimension is 2).  cycle_type 1, 3, 5 or 7; the smoother is relax_times l1-Jacobi sweeps with relax_weight; one application is
+ * max_iter cycles from a zero guess.  alpha / beta: the BoomerAMG on Pi^T A Pi (num_functions is set to dimension) and on G^T A G;
+ * NULL = hda_ams_default_amg_params.  A and G must outlive the handle.  The handle is accepted by the Krylov entries,
+ * hda_amg_vcycle and hda_precond_time as an ILU handle is. */
+void hda_ams_default_amg_params(hda_amg_params *p, int num_functions);
+int hda_ams_create(hda_csr_t A, hda_csr_t G, const double *c0, const double *c1, const double *c2, int dimension, int cycle_type,
+                   int relax_times, double relax_weight, int max_iter, const hda_amg_params *alpha, const hda_amg_params *beta,
+                   hda_amg_t *out);
+/* borrowed view: which 0 Pi, 1 G^T A G, 2 Pi^T A Pi (both after the zero-row repair) */
+int hda_ams_matrix(hda_amg_t h, int which, hda_csr_t *out);
+/* info[0..7]: n_e, n_v, nnz(Pi), nnz(A_G), nnz(A_Pi), repaired rows of A_G, of A_Pi, levels of B_G * 256 + levels of B_Pi;
+ * ms[0..4] (may be NULL): setup of Pi and the transposes, products and repair, B_G, B_Pi; algorithmic bytes of one application */
+int hda_ams_info(hda_amg_t h, int64_t info[8], double ms[5]);
 /* "preconditioner: mgr" (reference src/internal/mgr.c; MGRlvl_args include/internal/mgr.h:132-147): multigrid reduction
  * by dof labels with BoomerAMG on the coarsest system.  labels = dofmap of A's rows.  Implemented per level:
  * prolongation injection (0) / l1-jacobi (1) / jacobi (2); restriction injection (0) / jacobi (2) / columped (14);

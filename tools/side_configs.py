@@ -13,7 +13,10 @@ kernel's SURVEY 8(d) bytes / time, and `iters_match`: the same configuration on 
 iteration count == oracle's.  bench.py carries them as budgeted extras; `python tools/side_configs.py [mgr|ilu0] [size]` runs one.
 
   schwarz N       not a BASELINE config: GMRES(30) + RAS(1)-ILU(0) / RAS(1)-ILU(1) on the N^3 Laplacian, on the row
-                  blocks HDA_BLOCKS gives: setup ms by phase, ms per application, iterations (`python tools/side_configs.py schwarz 128`)"""
+                  blocks HDA_BLOCKS gives: setup ms by phase, ms per application, iterations (`python tools/side_configs.py schwarz 128`)
+  ams N           not a BASELINE config: PCG + AMS (examples/maxwell-ams.yml) on the definite Maxwell operator of
+                  tests/ams_reference.py (maxwell_fd, mass coefficient 1e-3) at N^3 nodes: iterations, ms per solve, setup seconds, the
+                  dominant kernel's bytes / time (`python tools/side_configs.py ams 64`)"""
 import json
 import os
 import sys
@@ -192,11 +195,54 @@ def gmres_schwarz(hh, n=128, reps=10):
     return out
 
 
+def pcg_ams(hh, n=64, steps=3, warmup=1):
+    """PCG(1e-8) + AMS through HYPREDRV_LinearSolverSetup / Apply with the solver block of examples/maxwell-ams.yml; G is an IJ matrix
+    with a column range of its own, the coordinates are IJ vectors."""
+    from hypredrive_amd import hypredrv as hd
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ams_reference as ar
+    p = ar.maxwell_fd(n, n, n, sigma=1e-3, seed=0)
+    N, nnz = p.A.shape[0], int(p.A.nnz)
+    h = hd.Hypredrv(open(os.path.join(ROOT, "examples", "maxwell-ams.yml")).read())
+    h.set_matrix_csr(0, N - 1, p.A.indptr, p.A.indices, p.A.data)
+    h.set_rhs_array(0, N - 1, np.random.default_rng(11).standard_normal(N))
+    h.finish_system()
+    handles = [hd.ij_matrix(p.G, 0, N)] + [hd.ij_vector(c, N) for c in p.coords]
+    h.set_discrete_gradient(handles[0])
+    h.set_coordinates(*handles[1:])
+    setup = _timed(hh, h, steps, warmup)
+    A = hh._lib.borrow_matrix(h)
+    hh.probe_spmv(None, 0)
+    pj, pr = hh._lib.probe_add(A, 2), hh._lib.probe_add(A, 1)
+    ms, last = _solves(hh, h, steps, warmup)
+    j_ms, j_n = hh._lib.probe_read_id(pj)
+    r_ms, r_n = hh._lib.probe_read_id(pr)
+    hh.probe_spmv(None, 0)
+    by = 12.0 * nnz + 4.0 * (N + 1) + 32.0 * N   # SURVEY 8(d): B_spmv + 16 n
+    by_r = 12.0 * nnz + 4.0 * (N + 1) + 24.0 * N
+    out = {"what": f"PCG + AMS (cycle 1, examples/maxwell-ams.yml) on the definite Maxwell operator of tests/ams_reference.py at {n}^3 nodes, "
+                   "mass coefficient 1e-3; parity unpinned (no reference output for AMS exists)",
+           "rows": N, "nnz": nnz, "nodes": n ** 3, "iters": last["iters"], "converged": last["converged"], "final_rel": last["final_rel"],
+           "ms_per_step": ms, "value": N / (ms * 1e-3), "unit": "DOF/s", "setup_s": setup[1] * 1e-3, "setup_cold_s": setup[0] * 1e-3,
+           "dominant_kernel": {"kernel": "l1-Jacobi sweep on A (the smoother of the edge space)", "bytes_per_launch": by, "avg_ms": j_ms, "launches": j_n,
+                               "gbs": by / j_ms / 1e6 if j_ms else None, "frac": by / j_ms / 1e6 / HBM_PEAK_GBS if j_ms else None},
+           "residual_on_A": {"kernel": "residual on A (before each subspace correction, and PCG's product)", "bytes_per_launch": by_r, "avg_ms": r_ms,
+                             "launches": r_n, "gbs": by_r / r_ms / 1e6 if r_ms else None}}
+    del A
+    h.destroy_solver()
+    h.close()
+    for q, v in enumerate(handles):
+        (hd.lib().HYPRE_IJMatrixDestroy if q == 0 else hd.lib().HYPRE_IJVectorDestroy)(v)
+    return out
+
+
 if __name__ == "__main__":
     import hypredrive_amd as hh
     which = sys.argv[1] if len(sys.argv) > 1 else "mgr"
     if which == "schwarz":
         print(json.dumps(gmres_schwarz(hh, int(sys.argv[2]) if len(sys.argv) > 2 else 128)))
+    elif which == "ams":
+        print(json.dumps(pcg_ams(hh, int(sys.argv[2]) if len(sys.argv) > 2 else 64)))
     elif which == "mgr":
         print(json.dumps(gmres_mgr(hh, int(sys.argv[2]) if len(sys.argv) > 2 else 512)))
     else:
