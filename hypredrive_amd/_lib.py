@@ -963,11 +963,12 @@ def air_restriction(A, cf, distance=2, strong_th=0.25, filter_th=0.0):
 
 def csr_form(A, nown=-1):
     """The kernel the product of A runs on: the whole product (nown < 0) or the owned-column half of the split product with nown
-    owned columns.  dict(kernel (a FORMS name), lpr, value_coded, escapes, rc_esc_rows, maxrow, blocks (chunks or windows))."""
+    owned columns.  dict(kernel (a FORMS name), lpr, value_coded, escapes, rc_esc_rows, maxrow, blocks (chunks or windows), vc_packed
+    (value-coded with packed escapes: the escape slots of its kernel, 512 or 640, else 0))."""
     info = np.zeros(8, dtype=np.int32)
     _check(load().hda_csr_form(A.h, nown, _ip(info)))
     return dict(kernel=FORMS[int(info[0])], lpr=int(info[1]), value_coded=bool(info[2]), escapes=int(info[3]),
-                rc_esc_rows=int(info[4]), maxrow=int(info[5]), blocks=int(info[6]))
+                rc_esc_rows=int(info[4]), maxrow=int(info[5]), blocks=int(info[6]), vc_packed=int(info[7]))
 
 
 def spmv_mode(A, mode, x, nown=-1, alpha=1.0, beta=0.0, yin=None, in_place=False, b=None, dinv=None, w=None, dinv2=None, y2=None):

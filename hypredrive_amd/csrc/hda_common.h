@@ -259,12 +259,20 @@ struct DCsr {
    // structured-grid operator in lexicographic order) ucol holds, per chunk, 2 * kWinRuns ints (first position, first column of
    // every run; unused runs start at INT_MAX) instead of the list: the kernel computes a position's column instead of loading it
    mutable bool                   win_runs = false;
+   // packed escapes of a value-coded operator in the list form (hda_kernels.hip "packed escapes"): the values outside the first
+   // vc_dict dictionary entries, chunk after chunk in entry order; the number of an escaped entry among its chunk's travels in its
+   // code byte (vc_dict .. 254) and in bits 10 - 15 of its position, and wmeta has FOUR ints per chunk, the fourth the chunk's first
+   // slot in vc_esc.  escapes keeps counting the entries outside the 255-entry dictionary.
+   mutable DArray<double>         vc_esc;        // vc_escapes (+ padding)
+   mutable int                    vc_pack = -1, vc_dict = 0, vc_maxesc = 0; // -1 not examined, 0 code 255 = read val[k], 1 packed; D; most escapes in a chunk
+   mutable long long              vc_escapes = 0; // entries outside the first vc_dict dictionary entries
    void reset_plan() const
    {
       chunk_row.release(); code.release(); dict_val.release(); dict_delta.release(); offd.reset();
-      rclass.release(); rc_keys.release(); lidx.release(); ucol.release(); wmeta.release();
+      rclass.release(); rc_keys.release(); lidx.release(); ucol.release(); wmeta.release(); vc_esc.release();
       gen = next_csr_gen();
       nchunks = 0; maxrow = -1; coded = -1; rowcoded = 0; rc_esc_rows = 0; rc_esc_entries = 0; win = -1; nwin = 0; win_maxu = 0; win_total = 0; win_runs = false;
+      vc_pack = -1; vc_dict = 0; vc_maxesc = 0; vc_escapes = 0;
    }
 };
 

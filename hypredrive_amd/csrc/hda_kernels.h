@@ -126,7 +126,8 @@ void lap7_generate(const int n[3], const int P[3], const int pc[3], const double
 // the kernel a product runs on; the values are the HDA_FORM_* ids of include/hypredrv_amd.h
 enum class SpmvForm : int { None = -1, LaneGroup = 0, Stream = 1, Window = 2, WindowRuns = 3, Coded = 4, RowClass = 5 };
 // info[0..7]: SpmvForm of the whole product (nown < 0) or of the owned-column half of the split one (nown >= 0), lanes per row of the
-// lane-group kernel, value-coded, escapes, CSR rows of a row-class operator, longest row, chunks or windows, 0
+// lane-group kernel, value-coded, escapes, CSR rows of a row-class operator, longest row, chunks or windows, escape slots of the kernel
+// (512 or 640) on a value-coded operator with packed escapes (else 0)
 void spmv_form_info(const DCsr &A, int nown, int info[8]);
 enum { SPMV_TEST_PLAIN = 0, SPMV_TEST_PLAIN_DOT = 1, SPMV_TEST_RESID = 2, SPMV_TEST_JACOBI = 3, SPMV_TEST_JACOBI_DOT = 4, SPMV_TEST_SCALED_COPY = 5 };
 // One product of the family through the entry the solver uses (nown < 0), or split as launch_spmv_halo splits it (nown >= 0: owned

@@ -1246,6 +1246,11 @@ __global__ __launch_bounds__(256) void k_spmv_rowclass(int nrows, const unsigned
 // columns per entry, 0.2-0.3 on Galerkin operators).  The streams and the distinct-column list of the NEXT chunk are
 // requested before the row reduction of the current one.
 constexpr int kWChunk = 1024, kWinSort = 2048; // kWinSort >= kWChunk + kMaxRowLds
+// packed escapes of a value-coded operator in the list form (ensure_vcpack): the first kVcDict dictionary entries keep their codes;
+// an entry outside them is escape s of its chunk (entry order), s = (code - kVcDict) + kVcRange * (position >> kVcPosBits), and its
+// value sits at vc_esc[e0 + s], e0 the fourth word of the chunk's (then four-word) wmeta entry.  At most kEscCap escapes in a chunk.
+constexpr int kEscCap = 640, kEscSlotsSmall = 512, kVcDict = 240, kVcRange = 255 - kVcDict, kVcPosBits = 10;
+static_assert(kVcRange * (1 << (16 - kVcPosBits)) >= kEscCap, "code range x spare position bits must number kEscCap slots");
 
 __global__ __launch_bounds__(256) void k_wchunk_rows(int nw, int nrows, const int *__restrict__ rowptr, int *__restrict__ wmeta)
 {
@@ -1497,7 +1502,12 @@ static void ensure_window(const DCsr &A)
 // trace that differs between the fast and the slow arms).  No instantiation may cross that line again unnoticed.
 // FOLD (last, for the same reason): the folded Jacobi sweep, as in k_spmv -- the row's own iterate comes from yin and travels one
 // chunk ahead in the place of x[r]
-template <int MODE, bool DOT, bool VC, bool SPLIT, bool RUNS = false, bool EPI = false, bool FOLD = false>
+// PACK (last, for the same reason; 0, or the escape slots in LDS: kEscSlotsSmall = 512 or kEscCap = 640): value-coded with packed escapes -- `val` is then the
+// operator's vc_esc and a chunk's wmeta entry has a fourth word, the first slot of its escapes.  The chunk's escaped values travel one
+// chunk ahead like the other streams (up to ceil(PACK / 256) doubles per lane, no load waits for a code) and land in LDS right behind the kVcDict
+// dictionary values, so that the value of an entry is sdict[code + kVcRange * (position >> 10)] whether it escaped or not (an entry
+// inside the dictionary has no high position bits)
+template <int MODE, bool DOT, bool VC, bool SPLIT, bool RUNS = false, bool EPI = false, bool FOLD = false, int PACK = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_spmv_win(int nw, const int *__restrict__ wmeta, const int *__restrict__ rowptr,
                                                   const unsigned short *__restrict__ lidx, const int *__restrict__ ucol,
                                                   const double *__restrict__ val, const double *__restrict__ x, double alpha, double beta,
@@ -1508,24 +1518,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_sp
 { // out2 (EPI, MODE_PLAIN only): a second result out2 = dinv2 .* out, as in k_spmv_stream (the next level's zero-guess Jacobi sweep)
    static_assert(!EPI || (MODE == MODE_PLAIN && !DOT && !SPLIT), "the scaled second result exists for whole plain products only");
    static_assert(!FOLD || (MODE == MODE_JACOBI && !DOT && !VC && !SPLIT && !RUNS), "the folded form exists for the whole Jacobi sweep on the list form alone");
+   static_assert(!PACK || (VC && !SPLIT && !RUNS), "packed escapes exist for whole products of a value-coded operator in the list form alone");
    extern __shared__ double smem[];
    double *prod = smem, *xs = smem + prod_len;
-   __shared__ double sdict[VC ? 256 : 1];
+   static_assert(PACK == 0 || PACK == kEscSlotsSmall || PACK == kEscCap, "escape slots in LDS: kEscSlotsSmall or kEscCap");
+   constexpr int WS = PACK ? 4 : 3, EU = PACK ? (PACK + 255) / 256 : 1; // words of a chunk's wmeta entry; escape slots per lane
+   __shared__ double sdict[PACK ? kVcDict + PACK : VC ? 256 : 1];
    if (VC)
    {
-      sdict[threadIdx.x] = dval[threadIdx.x];
+      if (!PACK || threadIdx.x < kVcDict) sdict[threadIdx.x] = dval[threadIdx.x];
       __syncthreads();
    }
    auto value = [&](int k) -> double { // value-coded operator: one-byte code into the dictionary, 255 = read the value array
-      if (VC) { const int q = code[k]; return (q != 255) ? sdict[q] : val[k]; }
+      if (VC && !PACK) { const int q = code[k]; return (q != 255) ? sdict[q] : val[k]; }
       return val[k];
    };
+   auto packed_value = [&](int q, int l) -> double { return sdict[q + kVcRange * (l >> kVcPosBits)]; }; // (PACK) code, raw position
+   auto position = [&](int l) -> int { return PACK ? (l & ((1 << kVcPosBits) - 1)) : l; };
    constexpr int E = 4, U = 3; // entries / distinct columns per thread requested one chunk ahead
    const int tid = threadIdx.x;
    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslot = gridDim.x >> 3;
    const int nper = (nw + 7) >> 3;
    double    acc  = 0.0;
-   struct Chunk { int r0, r1, k0, k1, u0, nu, q; bool ok; };
+   struct Chunk { int r0, r1, k0, k1, u0, nu, q, e0, ne; bool ok; };
    auto meta = [&](int i) {
       Chunk     c;
       const int q = xcd * nper + i;
@@ -1533,14 +1548,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_sp
       c.ok        = i < nper && q < nw;
       if (c.ok)
       {
-         c.r0 = wmeta[3 * q]; c.k0 = wmeta[3 * q + 1]; c.u0 = wmeta[3 * q + 2];
-         c.r1 = wmeta[3 * q + 3]; c.k1 = wmeta[3 * q + 4]; c.nu = wmeta[3 * q + 5] - c.u0;
+         c.r0 = wmeta[WS * q]; c.k0 = wmeta[WS * q + 1]; c.u0 = wmeta[WS * q + 2];
+         c.r1 = wmeta[WS * q + WS]; c.k1 = wmeta[WS * q + WS + 1]; c.nu = wmeta[WS * q + WS + 2] - c.u0;
+         if (PACK) { c.e0 = wmeta[WS * q + 3]; c.ne = wmeta[WS * q + WS + 3] - c.e0; }
       }
       else c.r0 = c.r1 = c.k0 = c.k1 = c.u0 = c.nu = 0;
+      if (!PACK || !c.ok) c.e0 = c.ne = 0;
       return c;
    };
-   double pv[E];
-   int    pl[E], pu[U];
+   double pv[PACK ? 1 : E], pesc[EU] = {}; // (PACK: the codes travel ahead in pq, the chunk's escaped values in pesc)
+   int    pl[E], pu[U], pq[PACK ? E : 1];
    // per-row operands of the lane's FIRST row of a chunk, requested with the chunk's streams (one chunk ahead): the row reduction
    // then starts on LDS products at once instead of on a round trip for its row pointers, and ends on registers instead of on a
    // round trip for b, dinv and x[r]  (pf: HDA_WIN_PF, A/B)
@@ -1569,8 +1586,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_sp
       for (int e = 0; e < E; e++)
       {
          const int k = c.k0 + tid + 256 * e;
-         pv[e]       = (k < c.k1) ? value(k) : 0.0;
+         if (PACK) pq[e] = (k < c.k1) ? (int)code[k] : 0;
+         else pv[e] = (k < c.k1) ? value(k) : 0.0;
          pl[e]       = (k < c.k1) ? (int)lidx[k] : 0;
+      }
+      if (PACK)
+      {
+#pragma unroll
+         for (int u = 0; u < EU; u++)
+         {
+            const int j = tid + 256 * u;
+            pesc[u]     = (j < c.ne) ? val[c.e0 + j] : 0.0;
+         }
       }
       if (RUNS) pu[0] = ((tid & 63) < 2 * kWinRuns) ? ucol[(size_t)c.q * 2 * kWinRuns + (tid & 63)] : 0x7fffffff; // the chunk's run table, once per wave
       else
@@ -1627,15 +1654,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_sp
             xs[j]        = (SPLIT && uc >= nown) ? 0.0 : x[uc];
          }
       }
+      if (PACK)
+      { // (read in stage 1 alone: two barriers lie between that and the next write)
+#pragma unroll
+         for (int u = 0; u < EU; u++)
+            if (256 * (u + 1) <= PACK || tid + 256 * u < PACK) sdict[kVcDict + tid + 256 * u] = pesc[u];
+      }
       __syncthreads();
       // stage 1: products -> LDS
 #pragma unroll
       for (int e = 0; e < E; e++)
       {
          const int k = tid + 256 * e;
-         if (k < ne) prod[k] = pv[e] * xs[pl[e]];
+         if (k < ne) prod[k] = (PACK ? packed_value(pq[e], pl[e]) : pv[e]) * xs[position(pl[e])];
       }
-      for (int k = tid + 256 * E; k < ne; k += 256) prod[k] = value(cur.k0 + k) * xs[lidx[cur.k0 + k]];
+      for (int k = tid + 256 * E; k < ne; k += 256)
+      {
+         if (PACK)
+         {
+            const int l = lidx[cur.k0 + k];
+            prod[k]     = packed_value(code[cur.k0 + k], l) * xs[position(l)];
+         }
+         else prod[k] = value(cur.k0 + k) * xs[lidx[cur.k0 + k]];
+      }
       // the next chunk's streams and distinct-column list leave now and travel during the reduction
       const Chunk nxt = meta(i + nslot);
       if (nxt.ok) request(nxt);
@@ -1948,6 +1989,180 @@ static void ensure_vcoded(const DCsr &A)
              100.0 * e / std::max(A.nnz, 1));
 }
 
+// ---- packed escapes (value-coded operator in the list form) -------------------------------------------
+// An escape (code 255) makes the product read val[k]: a 64-byte sector for 8 bytes, and a load that waits for the code.  At 8 - 10 %
+// escapes (the level-0 transfer operators) those sectors are as many bytes as the coding saves.  Here the escaped values of a chunk
+// are stored side by side, in entry order, and the number of an entry's escape rides in what the format already streams: codes
+// kVcDict .. 254 carry its remainder by kVcRange, the spare bits 10 - 15 of the 2-byte position (a chunk of at most 1024 distinct
+// columns) the quotient.  The chunks' blocks follow one another without padding -- the escapes are far from evenly spread: 100 per
+// chunk on average and over 400 in the chunks along the boundary of the grid -- and a chunk finds its block through a fourth word in
+// its wmeta entry.  The dictionary keeps its first kVcDict values (same ranking); the entries of the values it loses become escapes.
+// Same values, same products, same order of additions as the unpacked form.
+// pass 1: entries outside the first kVcDict dictionary entries, per chunk, and the most in one chunk
+__global__ __launch_bounds__(256) void k_vcpack_count(int nw, const int *__restrict__ wmeta, const unsigned char *__restrict__ code, int *__restrict__ ecount,
+                                                      int *mx)
+{
+   __shared__ int cnt;
+   for (int c = blockIdx.x; c < nw; c += gridDim.x)
+   {
+      if (threadIdx.x == 0) cnt = 0;
+      __syncthreads();
+      const int k0 = wmeta[3 * c + 1], k1 = wmeta[3 * c + 4];
+      int       mine = 0;
+      for (int k = k0 + threadIdx.x; k < k1; k += 256) mine += code[k] >= kVcDict;
+      if (mine) atomicAdd(&cnt, mine);
+      __syncthreads();
+      if (threadIdx.x == 0)
+      {
+         ecount[c] = cnt;
+         atomicMax(mx, cnt);
+      }
+      __syncthreads();
+   }
+}
+// the chunk table with a fourth word per chunk (first escape slot), and back
+__global__ __launch_bounds__(256) void k_vcpack_meta(int nw, const int *__restrict__ from, int from_words, int *__restrict__ to, int to_words,
+                                                     const int *__restrict__ eoff)
+{
+   const int c = blockIdx.x * 256 + threadIdx.x;
+   if (c > nw) return; // (entry nw: the sentinel)
+   for (int w = 0; w < 3; w++) to[to_words * c + w] = from[from_words * c + w];
+   if (to_words == 4) to[4 * c + 3] = eoff[c];
+}
+// pass 2 (every chunk has at most kEscCap escapes): number a chunk's escapes in entry order -- thread t owns the t-th run of
+// ceil(n / 256) entries -- move their values to the chunk's block and their numbers into code and position
+__global__ __launch_bounds__(256) void k_vcpack_fill(int nw, const int *__restrict__ wmeta4, const double *__restrict__ val, unsigned char *__restrict__ code,
+                                                     unsigned short *__restrict__ lidx, double *__restrict__ esc)
+{
+   __shared__ int scan[256];
+   const int      tid = threadIdx.x;
+   for (int c = blockIdx.x; c < nw; c += gridDim.x)
+   {
+      const int k0 = wmeta4[4 * c + 1], n = wmeta4[4 * c + 5] - k0, per = (n + 255) / 256;
+      const int e0 = wmeta4[4 * c + 3], ne = wmeta4[4 * c + 7] - e0;
+      const int a = k0 + min(n, tid * per), b = k0 + min(n, (tid + 1) * per);
+      int       cnt = 0;
+      for (int k = a; k < b; k++) cnt += code[k] >= kVcDict;
+      scan[tid] = cnt;
+      __syncthreads();
+      for (int o = 1; o < 256; o <<= 1)
+      {
+         const int v = (tid >= o) ? scan[tid - o] : 0;
+         __syncthreads();
+         scan[tid] += v;
+         __syncthreads();
+      }
+      int s = scan[tid] - cnt;
+      for (int k = a; k < b; k++)
+         if (code[k] >= kVcDict && s < ne)
+         {
+            esc[e0 + s] = val[k];
+            code[k]     = (unsigned char)(kVcDict + s % kVcRange);
+            lidx[k]     = (unsigned short)(lidx[k] | ((s / kVcRange) << kVcPosBits));
+            s++;
+         }
+      __syncthreads();
+   }
+}
+// back to the unpacked form (a split product wants it): a value among the dictionary entries kVcDict .. 254 gets its code again,
+// every other escape 255; positions lose their high bits
+__global__ __launch_bounds__(256) void k_vcpack_undo(int nw, const int *__restrict__ wmeta4, const double *__restrict__ esc, const double *__restrict__ dval,
+                                                     unsigned char *__restrict__ code, unsigned short *__restrict__ lidx)
+{
+   __shared__ long long tail[kVcRange];
+   if (threadIdx.x < kVcRange) tail[threadIdx.x] = __double_as_longlong(dval[kVcDict + threadIdx.x]);
+   __syncthreads();
+   for (int c = blockIdx.x; c < nw; c += gridDim.x)
+   {
+      const int k0 = wmeta4[4 * c + 1], k1 = wmeta4[4 * c + 5], e0 = wmeta4[4 * c + 3];
+      for (int k = k0 + threadIdx.x; k < k1; k += 256)
+      {
+         const int q = code[k];
+         if (q < kVcDict) continue;
+         const int       l    = lidx[k];
+         const long long bits = __double_as_longlong(esc[e0 + (q - kVcDict) + kVcRange * (l >> kVcPosBits)]);
+         int             nq   = 255;
+         for (int j = 0; j < kVcRange; j++)
+            if (tail[j] == bits) { nq = kVcDict + j; break; }
+         code[k] = (unsigned char)nq;
+         lidx[k] = (unsigned short)(l & ((1 << kVcPosBits) - 1));
+      }
+   }
+}
+// decided once per matrix, after ensure_vcoded and ensure_window: HDA_VC_PACK=0 (read per matrix) keeps the unpacked form.  A split
+// product (its kernels read code 255 -> val[k]) takes the packed form back, for good.
+static void ensure_vcpack(const DCsr &A, bool split)
+{
+   if (A.coded != 2 || A.win != 1 || A.win_runs) return;
+   const int nw = A.nwin, g = std::min(nw, 256 * 8);
+   if (split || A.offd)
+   {
+      if (A.vc_pack == 1)
+      {
+         k_vcpack_undo<<<g, 256, 0, STREAM>>>(nw, A.wmeta.data(), A.vc_esc.data(), A.dict_val.data(), A.code.data(), A.lidx.data());
+         DArray<int> w3(3 * ((size_t)nw + 2));
+         w3.zero();
+         k_vcpack_meta<<<ceil_div(nw + 1, 256), 256, 0, STREAM>>>(nw, A.wmeta.data(), 4, w3.data(), 3, nullptr);
+         Context::get().sync();
+         A.wmeta = std::move(w3);
+         A.vc_esc.release();
+         HDA_TRACE("value-coded SpMV for %d x %d, nnz %d: packed escapes taken back for a split product", A.nrows, A.ncols, A.nnz);
+      }
+      A.vc_pack = 0;
+      return;
+   }
+   if (A.vc_pack >= 0) return;
+   A.vc_pack = 0;
+   if (getenv("HDA_VC_PACK") && atoi(getenv("HDA_VC_PACK")) == 0)
+   {
+      HDA_TRACE("value-coded SpMV for %d x %d, nnz %d: unpacked form (HDA_VC_PACK=0), 255 dictionary values", A.nrows, A.ncols, A.nnz);
+      return;
+   }
+   if (A.win_maxu > (1 << kVcPosBits))
+   {
+      HDA_TRACE("value-coded SpMV for %d x %d, nnz %d: unpacked form (%d distinct columns in a chunk leave no spare position bits)", A.nrows, A.ncols,
+                A.nnz, A.win_maxu);
+      return;
+   }
+   DArray<int> ecount((size_t)nw + 1), eoff((size_t)nw + 2), mx(1);
+   ecount.zero();
+   mx.zero();
+   k_vcpack_count<<<g, 256, 0, STREAM>>>(nw, A.wmeta.data(), A.code.data(), ecount.data(), mx.data());
+   exclusive_scan(nw, ecount.data(), eoff.data(), nullptr);
+   int m = 0, total = 0;
+   mx.download(&m, 1);
+   HDA_HIP(hipMemcpyAsync(&total, eoff.data() + nw, 4, hipMemcpyDeviceToHost, STREAM));
+   Context::get().sync();
+   A.vc_dict    = kVcDict;
+   A.vc_maxesc  = m;
+   A.vc_escapes = total;
+   if (m > kEscCap)
+   {
+      HDA_TRACE("value-coded SpMV for %d x %d, nnz %d: unpacked form (D = %d would leave %d escapes in a chunk, %d slots)", A.nrows, A.ncols, A.nnz,
+                kVcDict, m, kEscCap);
+      return;
+   }
+   // the grid counts on eight workgroups per CU being resident (k_spmv_win): products, distinct x, dictionary + escape slots, dot partials
+   const size_t lds = sizeof(double) * ((size_t)kWChunk + A.maxrow + A.win_maxu + kVcDict + (m <= kEscSlotsSmall ? kEscSlotsSmall : kEscCap)) + 32;
+   if (8 * lds > 160 * 1024)
+   {
+      HDA_TRACE("value-coded SpMV for %d x %d, nnz %d: unpacked form (%zu bytes of LDS per workgroup with the escape slots: fewer than 8 per CU)",
+                A.nrows, A.ncols, A.nnz, lds);
+      return;
+   }
+   DArray<int> w4(4 * ((size_t)nw + 2));
+   w4.zero();
+   k_vcpack_meta<<<ceil_div(nw + 1, 256), 256, 0, STREAM>>>(nw, A.wmeta.data(), 3, w4.data(), 4, eoff.data());
+   A.vc_esc.alloc((size_t)total + kEscCap);
+   A.vc_esc.zero();
+   k_vcpack_fill<<<g, 256, 0, STREAM>>>(nw, w4.data(), A.val.data(), A.code.data(), A.lidx.data(), A.vc_esc.data());
+   Context::get().sync();
+   A.wmeta   = std::move(w4);
+   A.vc_pack = 1;
+   HDA_TRACE("value-coded SpMV for %d x %d, nnz %d: packed escapes, D = %d, %lld escapes (%.2f %%), at most %d in a chunk (%d slots in LDS)", A.nrows,
+             A.ncols, A.nnz, kVcDict, A.vc_escapes, 100.0 * (double)A.vc_escapes / std::max(A.nnz, 1), m, m <= kEscSlotsSmall ? kEscSlotsSmall : kEscCap);
+}
+
 static int spmv_mode()
 {
    static int m = -1;
@@ -2020,6 +2235,7 @@ static SpmvForm spmv_form(const DCsr &A, bool split)
    if (spmv_mode() == 0 && A.maxrow <= kMaxRowLds && !small)
    {
       ensure_window(A);
+      ensure_vcpack(A, split);
       if (A.win == 1) return A.win_runs ? SpmvForm::WindowRuns : SpmvForm::Window;
       return SpmvForm::Stream;
    }
@@ -2084,10 +2300,12 @@ static bool launch_spmv_impl(const DCsr &A_in, const double *x, double alpha, do
             g_epilogue.done = true;
          }
 #define HDA_WIN(VCF, SPF, RUNF, EPIF, CODE, DICT) HDA_WINF(VCF, SPF, RUNF, EPIF, false, CODE, DICT)
-#define HDA_WINF(VCF, SPF, RUNF, EPIF, FOLDF, CODE, DICT)                                                                                        \
-   k_spmv_win<MODE, DOT, VCF, SPF, RUNF, EPIF, FOLDF><<<wg, 256, wlds, STREAM>>>(A.nwin, A.wmeta.data(), A.rowptr.data(), A.lidx.data(),         \
-                                                                                 A.ucol.data(), A.val.data(), x, alpha, beta, yin, b, dinv, w,  \
-                                                                                 out, partial, nown, plen, CODE, DICT, win_pf(), wepi_d, wepi_o)
+#define HDA_WINF(VCF, SPF, RUNF, EPIF, FOLDF, CODE, DICT) HDA_WINV(VCF, SPF, RUNF, EPIF, FOLDF, 0, A.val.data(), CODE, DICT)
+#define HDA_WINV(VCF, SPF, RUNF, EPIF, FOLDF, PACKF, VAL, CODE, DICT)                                                                            \
+   k_spmv_win<MODE, DOT, VCF, SPF, RUNF, EPIF, FOLDF, PACKF><<<wg, 256, wlds, STREAM>>>(A.nwin, A.wmeta.data(), A.rowptr.data(), A.lidx.data(),  \
+                                                                                        A.ucol.data(), VAL, x, alpha, beta, yin, b, dinv, w,    \
+                                                                                        out, partial, nown, plen, CODE, DICT, win_pf(), wepi_d, \
+                                                                                        wepi_o)
          // (EPI exists for whole plain products without a dot alone: the constant keeps every other MODE / DOT from instantiating it)
          constexpr bool kEpi = MODE == MODE_PLAIN && !DOT;
          if (form == SpmvForm::WindowRuns)
@@ -2095,6 +2313,17 @@ static bool launch_spmv_impl(const DCsr &A_in, const double *x, double alpha, do
             if (split) { HDA_WIN(false, true, true, false, nullptr, nullptr); }
             else if (wepi) { HDA_WIN(false, false, true, kEpi, nullptr, nullptr); }
             else { HDA_WIN(false, false, true, false, nullptr, nullptr); }
+         }
+         else if (A.coded == 2 && A.vc_pack == 1)
+         { // packed escapes: the kernel's value array is the operator's vc_esc (spmv_form took the packed form back if this is a split product)
+            HDA_REQUIRE(!split, "split product on a value-coded operator with packed escapes");
+            if (A.vc_maxesc <= kEscSlotsSmall)
+            { // (the escape slots in LDS: kEscSlotsSmall, or kEscCap for an operator that has a chunk with more)
+               if (wepi) { HDA_WINV(true, false, false, kEpi, false, kEscSlotsSmall, A.vc_esc.data(), A.code.data(), A.dict_val.data()); }
+               else { HDA_WINV(true, false, false, false, false, kEscSlotsSmall, A.vc_esc.data(), A.code.data(), A.dict_val.data()); }
+            }
+            else if (wepi) { HDA_WINV(true, false, false, kEpi, false, kEscCap, A.vc_esc.data(), A.code.data(), A.dict_val.data()); }
+            else { HDA_WINV(true, false, false, false, false, kEscCap, A.vc_esc.data(), A.code.data(), A.dict_val.data()); }
          }
          else if (A.coded == 2)
          {
@@ -2111,6 +2340,7 @@ static bool launch_spmv_impl(const DCsr &A_in, const double *x, double alpha, do
          }
 #undef HDA_WIN
 #undef HDA_WINF
+#undef HDA_WINV
          return true;
       }
       const int    grid = DOT ? gmax : std::min(gmax, ((A.nchunks + 7) / 8) * 8);
@@ -2256,7 +2486,12 @@ void spmv_prepare(const DCsr &A)
    if (A.nrows == 0) return;
    ensure_plan(A);
    ensure_coded(A);
-   if (spmv_mode() == 0) ensure_window(A); // at setup, so that the "prec" timer pays for it, not the first solve
+   if (spmv_mode() == 0)
+   { // at setup, so that the "prec" timer pays for it, not the first solve
+      ensure_window(A);
+      // (among several ranks the first whole product decides: an operator that only ever runs split products is never packed)
+      if (Comm::world().size == 1) ensure_vcpack(A, false);
+   }
 }
 void spmv_probe_clear()
 {
@@ -2313,9 +2548,14 @@ double matrix_stream_bytes(const DCsr &A, bool format)
       ensure_coded(A);
       if (A.coded == 1 && A.rowcoded == 1) return 1.0 * A.nrows + 12.0 * (double)A.rc_esc_entries; // one class byte per row; CSR for the rest
       if (A.coded == 1) return 1.0 * A.nnz + 12.0 * A.escapes;
-      if (spmv_mode() == 0) ensure_window(A);
+      if (spmv_mode() == 0)
+      {
+         ensure_window(A);
+         if (Comm::world().size == 1) ensure_vcpack(A, false); // (as spmv_prepare)
+      }
       const double idx = (A.win == 1) ? 2.0 * A.nnz + (A.win_runs ? 8.0 * kWinRuns * A.nwin : 4.0 * (double)A.win_total) + 12.0 * A.nwin
                                       : 4.0 * A.nnz; // 2-byte positions + distinct columns (or run tables) + chunk table, or columns
+      if (A.coded == 2 && A.vc_pack == 1) return idx + 4.0 * A.nwin + 1.0 * A.nnz + 8.0 * (double)A.vc_escapes; // a fourth word per chunk, codes, the escaped values side by side
       if (A.coded == 2) return idx + 1.0 * A.nnz + 8.0 * A.escapes;
       if (A.win == 1) return idx + 8.0 * A.nnz;
    }
@@ -2405,7 +2645,7 @@ void spmv_form_info(const DCsr &A, int nown, int info[8])
    info[4]          = f == SpmvForm::RowClass ? A.rc_esc_rows : 0;
    info[5]          = A.maxrow;
    info[6]          = f == SpmvForm::Stream ? A.nchunks : (f == SpmvForm::Window || f == SpmvForm::WindowRuns) ? A.nwin : 0;
-   info[7]          = 0;
+   info[7]          = (A.coded == 2 && A.vc_pack == 1) ? (A.vc_maxesc <= kEscSlotsSmall ? kEscSlotsSmall : kEscCap) : 0; // packed escapes: the kernel's escape slots
 }
 
 void spmv_test_mode(const DCsr &A, int mode, int nown, double alpha, double beta, double *x, const double *yin, const double *b, const double *dinv,
