@@ -19,6 +19,7 @@
 #include <limits>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
@@ -1250,6 +1251,16 @@ constexpr int kWChunk = 1024, kWinSort = 2048; // kWinSort >= kWChunk + kMaxRowL
 // an entry outside them is escape s of its chunk (entry order), s = (code - kVcDict) + kVcRange * (position >> kVcPosBits), and its
 // value sits at vc_esc[e0 + s], e0 the fourth word of the chunk's (then four-word) wmeta entry.  At most kEscCap escapes in a chunk.
 constexpr int kEscCap = 640, kEscSlotsSmall = 512, kVcDict = 240, kVcRange = 255 - kVcDict, kVcPosBits = 10;
+// row operands of the windowed kernel requested one chunk ahead (the kernel's `pf` argument; 0: loaded in the row reduction).  Same-box
+// A/B, three rounds: level-1 Jacobi sweep at 256^3 0.4562 -> 0.4512 ms (-1.1 %), solve 34.53 -> 34.40 ms.
+constexpr int kWinPf = 1;
+// entries up to which a product runs on the lane-group kernel.  Same-box A/B, two rounds each: 1 000 000
+// entries: 64^3 2.12 -> 1.96 ms per solve, 128^3 5.50 -> 5.25, 256^3 34.66 -> 34.33; 100 000 and 4 000 000 both a little behind it.
+constexpr long kSmallNnz = 1000000;
+// grid of a product that shares the chip with its own halo transfer: one workgroup slot per CU is left free
+// (7 of 8 resident 256-thread workgroups), or the transfer kernel would only start when the product ends
+constexpr int kOverlapGrid = kRedBlocks / 8 * 7;
+static_assert(kOverlapGrid == 1792 && kOverlapGrid % 8 == 0, "a whole number of workgroups per XCD, 7 on each of 256 CUs");
 static_assert(kVcRange * (1 << (16 - kVcPosBits)) >= kEscCap, "code range x spare position bits must number kEscCap slots");
 
 __global__ __launch_bounds__(256) void k_wchunk_rows(int nw, int nrows, const int *__restrict__ rowptr, int *__restrict__ wmeta)
@@ -2163,250 +2174,182 @@ static void ensure_vcpack(const DCsr &A, bool split)
              A.ncols, A.nnz, kVcDict, A.vc_escapes, 100.0 * (double)A.vc_escapes / std::max(A.nnz, 1), m, m <= kEscSlotsSmall ? kEscSlotsSmall : kEscCap);
 }
 
-static int spmv_mode()
+// The plans a product of A needs, built on first use: the chunk plan and the stencil / value coding; with `windows` the windowed form
+// and the packed escapes of a value-coded operator as well.  split: the product is the owned-column half of a split one, which takes
+// a packed form back.  pack_if_one_rank (setup and the byte counts, which have no product at hand): among several ranks the first
+// whole product decides -- an operator that only ever runs split products is never packed.
+static void ensure_forms(const DCsr &A, bool windows, bool split = false, bool pack_if_one_rank = false)
 {
-   static int m = -1;
-   if (m < 0)
-   {
-      m = 0; // (1 forced the lane-group kernel everywhere: rounds 1-2)
-   }
-   return m;
+   ensure_plan(A);
+   ensure_coded(A);
+   if (!windows) return;
+   ensure_window(A);
+   if (!pack_if_one_rank || Comm::world().size == 1) ensure_vcpack(A, split);
 }
 
-// row operands of the windowed kernel requested one chunk ahead (HDA_WIN_PF=0: loaded in the row reduction).  Same-box A/B, three
-// rounds (tools/gpurun/r03_f.sh): level-1 Jacobi sweep at 256^3 0.4562 -> 0.4512 ms (-1.1 %), solve 34.53 -> 34.40 ms.
-static int win_pf()
-{
-   constexpr int v = 1;
-   return v;
-}
-// entries below which a product runs on the lane-group kernel (HDA_SMALL_NNZ; 0 = never).  Same-box A/B, two rounds each
-// (tools/gpurun/r03_e.sh): 1 000 000 entries: 64^3 2.12 -> 1.96 ms per solve, 128^3 5.50 -> 5.25, 256^3 34.66 -> 34.33;
-// 100 000 and 4 000 000 both a little behind it.
-static long small_nnz()
-{
-   constexpr long v = 1000000;
-   return v;
-}
-
-// grid of a product that shares the chip with its own halo transfer: one workgroup slot per CU is left free
-// (7 of 8 resident 256-thread workgroups), or the transfer kernel would only start when the product ends
-static int overlap_grid()
-{
-   static const int g = [] {
-      int         v = 1792;
-      v             = std::max(kRedBlocks / 2, std::min(kRedBlocks, v));
-      return v / 8 * 8;
-   }();
-   return g;
-}
-
-// nown < 0: the whole product.  nown >= 0: SPLIT -- entries with ghost columns (>= nown) are left to k_offd_fix
-// y = A x with a second result y2 = dinv2 .* y from the same kernel when the operator runs on the streaming kernel (else the
-// caller does the scaling itself): set by spmv_with_scaled_copy for the duration of one spmv() call
-struct SpmvEpilogue {
-   const double *dinv2 = nullptr;
-   double       *out2  = nullptr;
-   bool          done  = false;
-};
-#define g_epilogue (RankState<SpmvEpilogue>::get())
-// The Jacobi sweep after a prolongation in its folded storage form (jacobi_folded): for the one launch it is armed for, the sweep of
-// A streams M = P~ = P - D^-1 (A P) instead of A -- x is then the coarse correction and yin the row's own iterate.  The launch stays
-// a MODE_JACOBI launch on A: a probe armed on (A, Jacobi) brackets it like any other sweep of that operator
-struct SpmvFold {
-   const DCsr *M    = nullptr;
-   bool        done = false;
-};
-#define g_fold (RankState<SpmvFold>::get())
 static bool fold_form(SpmvForm f, const DCsr &M) { return (f == SpmvForm::LaneGroup || f == SpmvForm::Stream || f == SpmvForm::Window) && M.coded != 2; }
 
 // The kernel a product of A runs on (whole product, or the owned-column half of a split one), decided as launch_spmv_impl
 // launches: builds the plans it needs (chunk plan, stencil / value coding, windows) on first use.  hda_csr_form reports it.
 static SpmvForm spmv_form(const DCsr &A, bool split)
 {
-   ensure_plan(A);
-   ensure_coded(A);
-   if (A.coded == 1 && spmv_mode() == 0) return A.rowcoded == 1 ? SpmvForm::RowClass : SpmvForm::Coded;
+   ensure_forms(A, false);
+   if (A.coded == 1) return A.rowcoded == 1 ? SpmvForm::RowClass : SpmvForm::Coded;
    // Small operators (the coarse levels of a hierarchy; every level of a small problem) are latency-bound, not bandwidth-bound: what
    // a product costs there is its chain of dependent memory round trips.  The lane-group kernel has three (row pointer -> entries ->
    // x); the chunked LDS kernels five and two barriers (chunk table -> row pointers -> entries -> x -> products in LDS -> row
-   // pointers again).  Below small_nnz() entries the lane-group kernel runs (whole products only: it has no owned-column form).
-   const bool small = !split && A.coded != 1 && A.nnz <= small_nnz() && A.nnz > 0;
-   if (spmv_mode() == 0 && A.maxrow <= kMaxRowLds && !small)
+   // pointers again).  Up to kSmallNnz entries the lane-group kernel runs (whole products only: it has no owned-column form).
+   const bool small = !split && A.nnz <= kSmallNnz && A.nnz > 0;
+   if (A.maxrow <= kMaxRowLds && !small)
    {
-      ensure_window(A);
-      ensure_vcpack(A, split);
+      ensure_forms(A, true, split);
       if (A.win == 1) return A.win_runs ? SpmvForm::WindowRuns : SpmvForm::Window;
       return SpmvForm::Stream;
    }
    return split ? SpmvForm::None : SpmvForm::LaneGroup;
 }
 
+// What one product launch works on.  alpha, beta and yin belong to MODE_PLAIN, b to MODE_RESID and MODE_JACOBI, dinv to MODE_JACOBI,
+// w and partial to a launch with a fused dot.  The two extras are offers: the launch returns whether it took the one it was given.
+//   dinv2, out2: a second result out2 = dinv2 .* out from the same kernel (spmv_with_scaled_copy).  Taken by a whole MODE_PLAIN launch
+//     without a dot on every kernel but the two stencil-coded ones; else the caller does the scaling itself.
+//   fold: the Jacobi sweep after a prolongation in its folded storage form (jacobi_folded).  Taken by a whole MODE_JACOBI launch without
+//     a dot, which then streams *fold = P~ = P - D^-1 (A P) instead of A -- x is the coarse correction and yin the row's own iterate.
+//     The launch stays a MODE_JACOBI launch on A: a probe armed on (A, Jacobi) brackets it like any other sweep of that operator.
+struct SpmvCall {
+   SpmvCall(const double *x_, double *out_) : x(const_cast<double *>(x_)), out(out_) {}
+   double       *x; // with a halo plan the ghost tail of x is refreshed (callers pass writable vectors there)
+   double       *out;
+   double        alpha = 1.0, beta = 0.0;
+   const double *yin = nullptr, *b = nullptr, *dinv = nullptr, *w = nullptr;
+   double       *partial = nullptr;
+   const double *dinv2   = nullptr;
+   double       *out2    = nullptr;
+   const DCsr   *fold    = nullptr;
+};
+
+// The template arguments a product kernel exists for, beside MODE and DOT: every rule, once.  k_spmv_win has all six; k_spmv_stream
+// has VC, SPLIT and FOLD, k_spmv FOLD alone (their second result is a run-time argument) and the stencil-coded kernels SPLIT.
 template <int MODE, bool DOT>
-static bool launch_spmv_impl(const DCsr &A_in, const double *x, double alpha, double beta,
-                        const double *yin, const double *b, const double *dinv, const double *w,
-                        double *out, double *partial, int nown = -1)
+constexpr bool spmv_variant_ok(bool vc, bool split, bool runs, bool epi, bool fold, int pack)
 {
-   // (FOLD exists for the whole Jacobi sweep without a dot alone: the constant keeps every other MODE / DOT from instantiating it)
-   constexpr bool kFold = MODE == MODE_JACOBI && !DOT;
-   const bool     split = nown >= 0;
-   const bool     fold  = kFold && !split && g_fold.M;
-   const DCsr    &A     = fold ? *g_fold.M : A_in; // the matrix this launch streams
-   if (fold) g_fold.done = true;
-   if (A.nrows == 0 && !DOT) return true;
-   const SpmvForm form  = spmv_form(A, split);
+   if (epi && (split || MODE != MODE_PLAIN || DOT)) return false;                        // second result: whole plain products without a dot
+   if (fold && (vc || runs || split || epi || MODE != MODE_JACOBI || DOT)) return false; // folded: the uncoded whole Jacobi sweep, not the run form
+   if (runs && vc) return false;                                                         // the run form is never value-coded
+   if (pack != 0 && (!vc || split || runs)) return false;                                // packed escapes: whole value-coded products, list form
+   return true;
+}
+
+// Run-time launch options as template arguments.  OneOf<Vs...>{v} is an option v whose value is one of the constants Vs;
+// instantiate(f, a, b, ...) calls f(A, B, ...) with each option as the std::integral_constant of its value, which f can name as a
+// template argument.  f guards its launch with `if constexpr (spmv_variant_ok<...>(...))`, so that a combination without a kernel is
+// never instantiated -- it reaches spmv_no_kernel() instead.
+template <auto... Vs>
+struct OneOf {
+   std::common_type_t<decltype(Vs)...> v;
+};
+using Flag = OneOf<false, true>;
+template <class F>
+static void instantiate(F &&f) { f(); }
+template <class F, auto... Vs, class... Rest>
+static void instantiate(F &&f, OneOf<Vs...> a, Rest... rest)
+{
+   const bool listed = ((a.v == Vs && (instantiate([&](auto... c) { f(std::integral_constant<decltype(Vs), Vs>{}, c...); }, rest...), true)) || ...);
+   HDA_REQUIRE(listed, "product launch: an option has a value outside its list");
+}
+[[noreturn]] static void spmv_no_kernel() { throw Error("product launch: no kernel exists for this combination of options"); }
+
+// nown < 0: the whole product.  nown >= 0: SPLIT -- entries with ghost columns (>= nown) are left to k_offd_fix.
+// Returns whether the launch took the extra of c (the second result, or the fold).
+template <int MODE, bool DOT>
+static bool launch_spmv_impl(const DCsr &A_in, const SpmvCall &c, int nown = -1)
+{
+   const bool  split = nown >= 0;
+   const bool  fold  = MODE == MODE_JACOBI && !DOT && !split && c.fold;
+   const DCsr &A     = fold ? *c.fold : A_in; // the matrix this launch streams
+   if (A.nrows == 0 && !DOT) return fold;
+   const SpmvForm form = spmv_form(A, split);
+   // (the lane-group kernel -- very long rows -- has no split form: callers ask spmv_splittable and exchange first)
+   HDA_REQUIRE(form != SpmvForm::None, "split product on an operator that has no split form");
    HDA_REQUIRE(!fold || fold_form(form, A), "folded sweep armed on an operator whose storage form has no folded kernel");
-   const int      gmax  = split ? overlap_grid() : kRedBlocks;
-   if (form == SpmvForm::RowClass || form == SpmvForm::Coded)
+   // the variant of the form's kernel, as plain data
+   const bool stencil = form == SpmvForm::RowClass || form == SpmvForm::Coded;
+   const bool runs    = form == SpmvForm::WindowRuns;
+   const bool vc      = A.coded == 2 && (form == SpmvForm::Stream || form == SpmvForm::Window);
+   // packed escapes: the escape slots in LDS, kEscSlotsSmall, or kEscCap for an operator that has a chunk with more
+   const int pack = (vc && form == SpmvForm::Window && A.vc_pack == 1) ? (A.vc_maxesc <= kEscSlotsSmall ? kEscSlotsSmall : kEscCap) : 0;
+   // (spmv_form took the packed form back if this is a split product)
+   HDA_REQUIRE(!(split && pack), "split product on a value-coded operator with packed escapes");
+   // the scaled second result: in k_spmv_win an instantiation of its own (EPI) -- a launch that does not take it runs a kernel
+   // without any dinv2 / out2 code -- in k_spmv_stream and k_spmv the two pointers
+   const bool     epi   = MODE == MODE_PLAIN && !DOT && !split && c.out2 && !stencil;
+   const double  *dinv2 = epi ? c.dinv2 : nullptr;
+   double        *out2  = epi ? c.out2 : nullptr;
+   const auto    *code  = vc ? A.code.data() : nullptr;
+   const double  *dict  = vc ? A.dict_val.data() : nullptr;
+   const int      gmax  = split ? kOverlapGrid : kRedBlocks;
+   if (stencil)
    {
       const int per  = (((A.nrows + 7) >> 3) + 255) / 256 * 256; // rows per XCD (as in the kernel)
       const int grid = DOT ? gmax : std::min(gmax, 8 * (per / 256));
-      if (form == SpmvForm::RowClass)
-      {
-#define HDA_RC(SPF)                                                                                                                              \
-   k_spmv_rowclass<MODE, DOT, SPF><<<grid, 256, 0, STREAM>>>(A.nrows, A.rclass.data(), A.rc_keys.data(), A.dict_val.data(), A.dict_delta.data(),   \
-                                                             A.rowptr.data(), A.col.data(), A.val.data(), x, alpha, beta, yin, b, dinv, w, out,    \
-                                                             partial, nown)
-         if (split) HDA_RC(true);
-         else HDA_RC(false);
-#undef HDA_RC
-         return true;
-      }
-      if (split)
-         k_spmv_coded_row<MODE, DOT, true><<<grid, 256, 0, STREAM>>>(A.nrows, A.rowptr.data(), A.code.data(), A.dict_val.data(), A.dict_delta.data(),
-                                                                     A.col.data(), A.val.data(), x, alpha, beta, yin, b, dinv, w, out, partial, nown);
-      else
-         k_spmv_coded_row<MODE, DOT, false><<<grid, 256, 0, STREAM>>>(A.nrows, A.rowptr.data(), A.code.data(), A.dict_val.data(), A.dict_delta.data(),
-                                                                      A.col.data(), A.val.data(), x, alpha, beta, yin, b, dinv, w, out, partial, 0);
-      return true;
+      instantiate(
+         [&](auto SPLIT) {
+            if (form == SpmvForm::RowClass)
+               k_spmv_rowclass<MODE, DOT, SPLIT><<<grid, 256, 0, STREAM>>>(A.nrows, A.rclass.data(), A.rc_keys.data(), A.dict_val.data(),
+                                                                           A.dict_delta.data(), A.rowptr.data(), A.col.data(), A.val.data(), c.x,
+                                                                           c.alpha, c.beta, c.yin, c.b, c.dinv, c.w, c.out, c.partial, nown);
+            else
+               k_spmv_coded_row<MODE, DOT, SPLIT><<<grid, 256, 0, STREAM>>>(A.nrows, A.rowptr.data(), A.code.data(), A.dict_val.data(),
+                                                                            A.dict_delta.data(), A.col.data(), A.val.data(), c.x, c.alpha, c.beta,
+                                                                            c.yin, c.b, c.dinv, c.w, c.out, c.partial, SPLIT ? nown : 0);
+         },
+         Flag{split});
    }
-   if (form == SpmvForm::Stream || form == SpmvForm::Window || form == SpmvForm::WindowRuns)
+   else if (form == SpmvForm::Window || form == SpmvForm::WindowRuns)
    {
-      if (form != SpmvForm::Stream)
-      {
-         const int    plen = kWChunk + A.maxrow;
-         const size_t wlds = sizeof(double) * (size_t)(plen + A.win_maxu);
-         const int    wg   = DOT ? gmax : std::min(gmax, ((A.nwin + 7) / 8) * 8);
-         // a scaled second result asked for by spmv_with_scaled_copy (whole products only, not the owned-column half): its own
-         // instantiation (EPI) -- a launch that is not armed runs a kernel without any dinv2 / out2 code
-         bool          wepi   = false;
-         const double *wepi_d = nullptr;
-         double       *wepi_o = nullptr;
-         if (MODE == MODE_PLAIN && !DOT && !split && g_epilogue.out2)
-         {
-            wepi   = true;
-            wepi_d = g_epilogue.dinv2;
-            wepi_o = g_epilogue.out2;
-            g_epilogue.done = true;
-         }
-#define HDA_WIN(VCF, SPF, RUNF, EPIF, CODE, DICT) HDA_WINF(VCF, SPF, RUNF, EPIF, false, CODE, DICT)
-#define HDA_WINF(VCF, SPF, RUNF, EPIF, FOLDF, CODE, DICT) HDA_WINV(VCF, SPF, RUNF, EPIF, FOLDF, 0, A.val.data(), CODE, DICT)
-#define HDA_WINV(VCF, SPF, RUNF, EPIF, FOLDF, PACKF, VAL, CODE, DICT)                                                                            \
-   k_spmv_win<MODE, DOT, VCF, SPF, RUNF, EPIF, FOLDF, PACKF><<<wg, 256, wlds, STREAM>>>(A.nwin, A.wmeta.data(), A.rowptr.data(), A.lidx.data(),  \
-                                                                                        A.ucol.data(), VAL, x, alpha, beta, yin, b, dinv, w,    \
-                                                                                        out, partial, nown, plen, CODE, DICT, win_pf(), wepi_d, \
-                                                                                        wepi_o)
-         // (EPI exists for whole plain products without a dot alone: the constant keeps every other MODE / DOT from instantiating it)
-         constexpr bool kEpi = MODE == MODE_PLAIN && !DOT;
-         if (form == SpmvForm::WindowRuns)
-         { // run form (never value-coded)
-            if (split) { HDA_WIN(false, true, true, false, nullptr, nullptr); }
-            else if (wepi) { HDA_WIN(false, false, true, kEpi, nullptr, nullptr); }
-            else { HDA_WIN(false, false, true, false, nullptr, nullptr); }
-         }
-         else if (A.coded == 2 && A.vc_pack == 1)
-         { // packed escapes: the kernel's value array is the operator's vc_esc (spmv_form took the packed form back if this is a split product)
-            HDA_REQUIRE(!split, "split product on a value-coded operator with packed escapes");
-            if (A.vc_maxesc <= kEscSlotsSmall)
-            { // (the escape slots in LDS: kEscSlotsSmall, or kEscCap for an operator that has a chunk with more)
-               if (wepi) { HDA_WINV(true, false, false, kEpi, false, kEscSlotsSmall, A.vc_esc.data(), A.code.data(), A.dict_val.data()); }
-               else { HDA_WINV(true, false, false, false, false, kEscSlotsSmall, A.vc_esc.data(), A.code.data(), A.dict_val.data()); }
-            }
-            else if (wepi) { HDA_WINV(true, false, false, kEpi, false, kEscCap, A.vc_esc.data(), A.code.data(), A.dict_val.data()); }
-            else { HDA_WINV(true, false, false, false, false, kEscCap, A.vc_esc.data(), A.code.data(), A.dict_val.data()); }
-         }
-         else if (A.coded == 2)
-         {
-            if (split) { HDA_WIN(true, true, false, false, A.code.data(), A.dict_val.data()); }
-            else if (wepi) { HDA_WIN(true, false, false, kEpi, A.code.data(), A.dict_val.data()); }
-            else { HDA_WIN(true, false, false, false, A.code.data(), A.dict_val.data()); }
-         }
-         else
-         {
-            if (split) { HDA_WIN(false, true, false, false, nullptr, nullptr); }
-            else if (wepi) { HDA_WIN(false, false, false, kEpi, nullptr, nullptr); }
-            else if (fold) { HDA_WINF(false, false, false, false, kFold, nullptr, nullptr); }
-            else { HDA_WIN(false, false, false, false, nullptr, nullptr); }
-         }
-#undef HDA_WIN
-#undef HDA_WINF
-#undef HDA_WINV
-         return true;
-      }
+      const int     plen = kWChunk + A.maxrow;
+      const size_t  wlds = sizeof(double) * (size_t)(plen + A.win_maxu);
+      const int     wg   = DOT ? gmax : std::min(gmax, ((A.nwin + 7) / 8) * 8);
+      const double *val  = pack ? A.vc_esc.data() : A.val.data(); // packed escapes: the kernel's value array is the operator's vc_esc
+      instantiate(
+         [&](auto VC, auto SPLIT, auto RUNS, auto EPI, auto FOLD, auto PACK) {
+            if constexpr (spmv_variant_ok<MODE, DOT>(VC, SPLIT, RUNS, EPI, FOLD, PACK))
+               k_spmv_win<MODE, DOT, VC, SPLIT, RUNS, EPI, FOLD, PACK><<<wg, 256, wlds, STREAM>>>(
+                  A.nwin, A.wmeta.data(), A.rowptr.data(), A.lidx.data(), A.ucol.data(), val, c.x, c.alpha, c.beta, c.yin, c.b, c.dinv, c.w, c.out,
+                  c.partial, nown, plen, code, dict, kWinPf, dinv2, out2);
+            else spmv_no_kernel();
+         },
+         Flag{vc}, Flag{split}, Flag{runs}, Flag{epi}, Flag{fold}, OneOf<0, kEscSlotsSmall, kEscCap>{pack});
+   }
+   else if (form == SpmvForm::Stream)
+   {
       const int    grid = DOT ? gmax : std::min(gmax, ((A.nchunks + 7) / 8) * 8);
       const size_t lds  = sizeof(double) * (size_t)(kChunk + A.maxrow);
-      // a scaled second result asked for by spmv_with_scaled_copy: taken here (whole products only, not the owned-column half)
-      const double *epi_d = nullptr;
-      double       *epi_o = nullptr;
-      if (MODE == MODE_PLAIN && !DOT && !split && g_epilogue.out2)
-      {
-         epi_d = g_epilogue.dinv2;
-         epi_o = g_epilogue.out2;
-         g_epilogue.done = true;
-      }
-#define HDA_STREAM(VCF, SPF, CODE, DICT) HDA_STREAMF(VCF, SPF, false, CODE, DICT)
-#define HDA_STREAMF(VCF, SPF, FOLDF, CODE, DICT)                                                                                           \
-   k_spmv_stream<MODE, DOT, VCF, SPF, FOLDF><<<grid, 256, lds, STREAM>>>(A.nchunks, A.chunk_row.data(), A.rowptr.data(), A.col.data(),      \
-                                                                         A.val.data(), x, alpha, beta, yin, b, dinv, w, out, partial, CODE, \
-                                                                         DICT, nown, epi_d, epi_o)
-      if (A.coded == 2)
-      {
-         if (split) HDA_STREAM(true, true, A.code.data(), A.dict_val.data());
-         else HDA_STREAM(true, false, A.code.data(), A.dict_val.data());
-      }
-      else
-      {
-         if (split) HDA_STREAM(false, true, nullptr, nullptr);
-         else if (fold) HDA_STREAMF(false, false, kFold, nullptr, nullptr);
-         else HDA_STREAM(false, false, nullptr, nullptr);
-      }
-#undef HDA_STREAM
-#undef HDA_STREAMF
-      return true;
+      instantiate(
+         [&](auto VC, auto SPLIT, auto FOLD) {
+            if constexpr (spmv_variant_ok<MODE, DOT>(VC, SPLIT, false, false, FOLD, 0))
+               k_spmv_stream<MODE, DOT, VC, SPLIT, FOLD><<<grid, 256, lds, STREAM>>>(A.nchunks, A.chunk_row.data(), A.rowptr.data(), A.col.data(),
+                                                                                     A.val.data(), c.x, c.alpha, c.beta, c.yin, c.b, c.dinv, c.w,
+                                                                                     c.out, c.partial, code, dict, nown, dinv2, out2);
+            else spmv_no_kernel();
+         },
+         Flag{vc}, Flag{split}, Flag{fold});
    }
-   if (form == SpmvForm::None) return false; // the lane-group kernel (very long rows, HDA_SPMV=vector) has no split form: caller exchanges first
-   const int lpr  = pick_lpr(A);
-   long      need = ((long)A.nrows * lpr + 511) / 512; // two rows per group
-   int       grid = DOT ? kRedBlocks : (int)std::min<long>(std::max<long>(need, 1), kRedBlocks);
-   const double *vepi_d = nullptr;
-   double       *vepi_o = nullptr;
-   if (MODE == MODE_PLAIN && !DOT && g_epilogue.out2)
-   { // the scaled second result of spmv_with_scaled_copy
-      vepi_d = g_epilogue.dinv2;
-      vepi_o = g_epilogue.out2;
-      g_epilogue.done = true;
+   else
+   { // the lane-group kernel
+      const int  lpr  = pick_lpr(A);
+      const long need = ((long)A.nrows * lpr + 511) / 512; // two rows per group
+      const int  grid = DOT ? kRedBlocks : (int)std::min<long>(std::max<long>(need, 1), kRedBlocks);
+      instantiate(
+         [&](auto LPR, auto FOLD) {
+            if constexpr (spmv_variant_ok<MODE, DOT>(false, false, false, false, FOLD, 0))
+               k_spmv<LPR, MODE, DOT, FOLD><<<grid, 256, 0, STREAM>>>(A.nrows, A.rowptr.data(), A.col.data(), A.val.data(), c.x, c.alpha, c.beta,
+                                                                      c.yin, c.b, c.dinv, c.w, c.out, c.partial, dinv2, out2);
+            else spmv_no_kernel();
+         },
+         OneOf<4, 8, 16, 32, 64>{lpr}, Flag{fold});
    }
-#define HDA_LAUNCH(L)                                                                                   \
-   do {                                                                                                 \
-      if (fold)                                                                                         \
-         k_spmv<L, MODE, DOT, kFold><<<grid, 256, 0, STREAM>>>(A.nrows, A.rowptr.data(), A.col.data(),   \
-                                                               A.val.data(), x, alpha, beta, yin, b,    \
-                                                               dinv, w, out, partial, vepi_d, vepi_o);  \
-      else                                                                                              \
-         k_spmv<L, MODE, DOT><<<grid, 256, 0, STREAM>>>(A.nrows, A.rowptr.data(), A.col.data(),          \
-                                                        A.val.data(), x, alpha, beta, yin, b, dinv,     \
-                                                        w, out, partial, vepi_d, vepi_o);               \
-   } while (0)
-   switch (lpr)
-   {
-      case 4: HDA_LAUNCH(4); break;
-      case 8: HDA_LAUNCH(8); break;
-      case 16: HDA_LAUNCH(16); break;
-      case 32: HDA_LAUNCH(32); break;
-      default: HDA_LAUNCH(64); break;
-   }
-#undef HDA_LAUNCH
-   return true;
+   return epi || fold;
 }
 
 // Default: products overlap their ghost refresh on transports whose exchange only ENQUEUES work (RCCL).  On the host-staged
@@ -2424,53 +2367,51 @@ static bool overlap_enabled()
 // kMaxRowLds on an operator that is not stencil-coded), which has no owned-column form
 static bool spmv_splittable(const DCsr &A)
 {
-   ensure_plan(A);
-   ensure_coded(A);
-   return spmv_mode() == 0 && (A.coded == 1 || A.maxrow <= kMaxRowLds);
+   ensure_forms(A, false);
+   return A.coded == 1 || A.maxrow <= kMaxRowLds;
 }
 
 // Split product of a splittable A with nown owned columns, ghost-column part ensure_offd(A, nown) built:
 //   rows' owned-column part (SPLIT kernel) | between() | ghost-column part (k_offd_fix)
 // between() is where a row-partitioned product refreshes the ghost tail of x (launch_spmv_halo); x holds every column afterwards.
 template <int MODE, bool DOT, class Between>
-static void launch_spmv_split(const DCsr &A, int nown, double *x, double alpha, double beta, const double *yin, const double *b,
-                              const double *dinv, const double *w, double *out, double *partial, Between &&between)
+static bool launch_spmv_split(const DCsr &A, int nown, const SpmvCall &c, Between &&between)
 {
-   const OffdPart &O = *A.offd;
-   launch_spmv_impl<MODE, DOT>(A, x, alpha, beta, yin, b, dinv, w, out, partial, nown);
+   const OffdPart &O     = *A.offd;
+   const bool      taken = launch_spmv_impl<MODE, DOT>(A, c, nown);
    between();
    if (O.nbrows)
    {
       const int g = std::min(ceil_div(O.nbrows, 256), DOT ? kRedBlocks / 2 : 4096);
-      k_offd_fix<MODE, DOT><<<g, 256, 0, STREAM>>>(O.nbrows, O.brow.data(), O.rp.data(), O.col.data(), O.val.data(), x, alpha, b, dinv, w, out,
-                                                   partial);
+      k_offd_fix<MODE, DOT><<<g, 256, 0, STREAM>>>(O.nbrows, O.brow.data(), O.rp.data(), O.col.data(), O.val.data(), c.x, c.alpha, c.b, c.dinv, c.w,
+                                                   c.out, c.partial);
    }
+   return taken;
 }
 
 // Row-partitioned product with the ghost refresh of x under it (SURVEY 2.4 C1 "overlapped with the diag-block SpMV"):
 //   pack the send buffer | rows' owned-column part (SPLIT kernel) || transfer on the communication stream | ghost-column part
 // halo == nullptr or a one-rank run: the plain product.
 template <int MODE, bool DOT>
-static void launch_spmv_halo(const DCsr &A, const HaloPlan *halo, double *x, double alpha, double beta, const double *yin, const double *b,
-                             const double *dinv, const double *w, double *out, double *partial)
+static bool launch_spmv_halo(const DCsr &A, const HaloPlan *halo, const SpmvCall &c)
 {
    const bool active = halo && halo_active(*halo);
-   if (active && overlap_enabled() && !(MODE == MODE_PLAIN && beta != 0.0 && out == x))
+   if (active && overlap_enabled() && !(MODE == MODE_PLAIN && c.beta != 0.0 && c.out == c.x))
    {
       if (spmv_splittable(A))
       {
          ensure_offd(A, halo->nloc);
-         halo_pack(*halo, x);
-         launch_spmv_split<MODE, DOT>(A, halo->nloc, x, alpha, beta, yin, b, dinv, w, out, partial, [&] {
-            halo_transfer(*halo, x); // waits for the pack only; RCCL: enqueued, runs beside the kernel above; staged: host-side while it runs
+         halo_pack(*halo, c.x);
+         const bool taken = launch_spmv_split<MODE, DOT>(A, halo->nloc, c, [&] {
+            halo_transfer(*halo, c.x); // waits for the pack only; RCCL: enqueued, runs beside the kernel above; staged: host-side while it runs
             halo_wait(*halo);
          });
          Comm::world().stats.overlapped++;
-         return;
+         return taken;
       }
    }
-   if (active) halo_exchange(*halo, x);
-   launch_spmv_impl<MODE, DOT>(A, x, alpha, beta, yin, b, dinv, w, out, partial);
+   if (active) halo_exchange(*halo, c.x);
+   return launch_spmv_impl<MODE, DOT>(A, c);
 }
 
 namespace {
@@ -2479,33 +2420,26 @@ struct SpmvProbe {
    int                     mode = -1;
    std::vector<hipEvent_t> evs;
 };
-#define g_probes (RankState<std::vector<SpmvProbe>>::get())
+std::vector<SpmvProbe> &probes() { return RankState<std::vector<SpmvProbe>>::get(); }
 } // namespace
 void spmv_prepare(const DCsr &A)
 {
    if (A.nrows == 0) return;
-   ensure_plan(A);
-   ensure_coded(A);
-   if (spmv_mode() == 0)
-   { // at setup, so that the "prec" timer pays for it, not the first solve
-      ensure_window(A);
-      // (among several ranks the first whole product decides: an operator that only ever runs split products is never packed)
-      if (Comm::world().size == 1) ensure_vcpack(A, false);
-   }
+   ensure_forms(A, true, false, true); // at setup, so that the "prec" timer pays for it, not the first solve
 }
 void spmv_probe_clear()
 {
-   for (SpmvProbe &p : g_probes)
+   for (SpmvProbe &p : probes())
       for (hipEvent_t e : p.evs) (void)hipEventDestroy(e);
-   g_probes.clear();
+   probes().clear();
 }
 int spmv_probe_add(const DCsr *A, int mode)
 {
    SpmvProbe p;
    p.A    = A;
    p.mode = mode;
-   g_probes.push_back(p);
-   return (int)g_probes.size() - 1;
+   probes().push_back(p);
+   return (int)probes().size() - 1;
 }
 void spmv_probe_set(const DCsr *A, int mode)
 {
@@ -2517,9 +2451,9 @@ void spmv_probe_read(int id, double *avg_ms, int *count)
    Context::get().sync();
    double s = 0.0;
    int    c = 0;
-   if (id >= 0 && id < (int)g_probes.size())
+   if (id >= 0 && id < (int)probes().size())
    {
-      const SpmvProbe &p = g_probes[(size_t)id];
+      const SpmvProbe &p = probes()[(size_t)id];
       for (size_t e = 0; e + 1 < p.evs.size(); e += 2)
       {
          float ms = 0.f;
@@ -2534,8 +2468,7 @@ double rowptr_stream_bytes(const DCsr &A, bool format)
 {
    if (format)
    {
-      ensure_plan(A);
-      ensure_coded(A);
+      ensure_forms(A, false);
       if (A.coded == 1 && A.rowcoded == 1) return 8.0 * A.rc_esc_rows; // class rows never touch the row pointer
    }
    return 4.0 * (A.nrows + 1.0);
@@ -2544,15 +2477,10 @@ double matrix_stream_bytes(const DCsr &A, bool format)
 {
    if (format)
    {
-      ensure_plan(A);
-      ensure_coded(A);
+      ensure_forms(A, false);
       if (A.coded == 1 && A.rowcoded == 1) return 1.0 * A.nrows + 12.0 * (double)A.rc_esc_entries; // one class byte per row; CSR for the rest
       if (A.coded == 1) return 1.0 * A.nnz + 12.0 * A.escapes;
-      if (spmv_mode() == 0)
-      {
-         ensure_window(A);
-         if (Comm::world().size == 1) ensure_vcpack(A, false); // (as spmv_prepare)
-      }
+      ensure_forms(A, true, false, true);
       const double idx = (A.win == 1) ? 2.0 * A.nnz + (A.win_runs ? 8.0 * kWinRuns * A.nwin : 4.0 * (double)A.win_total) + 12.0 * A.nwin
                                       : 4.0 * A.nnz; // 2-byte positions + distinct columns (or run tables) + chunk table, or columns
       if (A.coded == 2 && A.vc_pack == 1) return idx + 4.0 * A.nwin + 1.0 * A.nnz + 8.0 * (double)A.vc_escapes; // a fourth word per chunk, codes, the escaped values side by side
@@ -2563,64 +2491,65 @@ double matrix_stream_bytes(const DCsr &A, bool format)
 }
 
 template <int MODE, bool DOT>
-static void launch_spmv(const DCsr &A, const HaloPlan *halo, const double *x, double alpha, double beta, const double *yin, const double *b,
-                        const double *dinv, const double *w, double *out, double *partial)
+static bool launch_spmv(const DCsr &A, const HaloPlan *halo, const SpmvCall &c)
 {
-   double *xw = const_cast<double *>(x); // with a halo plan the ghost tail of x is refreshed (callers pass writable vectors there)
-   for (SpmvProbe &p : g_probes)
+   for (SpmvProbe &p : probes())
       if (p.A == &A && p.mode == MODE && p.evs.size() < 8192)
       {
          hipEvent_t e0, e1;
          HDA_HIP(hipEventCreate(&e0));
          HDA_HIP(hipEventCreate(&e1));
          HDA_HIP(hipEventRecord(e0, STREAM));
-         launch_spmv_halo<MODE, DOT>(A, halo, xw, alpha, beta, yin, b, dinv, w, out, partial);
+         const bool taken = launch_spmv_halo<MODE, DOT>(A, halo, c);
          HDA_HIP(hipEventRecord(e1, STREAM));
          p.evs.push_back(e0);
          p.evs.push_back(e1);
-         return;
+         return taken;
       }
-   launch_spmv_halo<MODE, DOT>(A, halo, xw, alpha, beta, yin, b, dinv, w, out, partial);
+   return launch_spmv_halo<MODE, DOT>(A, halo, c);
 }
 
 void spmv(const DCsr &A, double alpha, const double *x, double beta, const double *y_in, double *y_out, const HaloPlan *halo)
 {
-   launch_spmv<MODE_PLAIN, false>(A, halo, x, alpha, beta, y_in, nullptr, nullptr, nullptr, y_out, nullptr);
+   SpmvCall c(x, y_out);
+   c.alpha = alpha;
+   c.beta  = beta;
+   c.yin   = y_in;
+   launch_spmv<MODE_PLAIN, false>(A, halo, c);
 }
-namespace {
-struct EpilogueArmed { // disarmed on every way out: a throwing launch must not leave a stale out2 behind for the next plain product
-   EpilogueArmed(const double *d, double *o) { g_epilogue = SpmvEpilogue{d, o, false}; }
-   ~EpilogueArmed() { g_epilogue = SpmvEpilogue{}; }
-};
-} // namespace
 bool spmv_with_scaled_copy(const DCsr &A, const double *x, double *y, const double *dinv2, double *y2, const HaloPlan *halo)
 {
-   EpilogueArmed armed(dinv2, y2);
-   launch_spmv<MODE_PLAIN, false>(A, halo, x, 1.0, 0.0, nullptr, nullptr, nullptr, nullptr, y, nullptr);
-   return g_epilogue.done;
+   SpmvCall c(x, y);
+   c.dinv2 = dinv2;
+   c.out2  = y2;
+   return launch_spmv<MODE_PLAIN, false>(A, halo, c);
 }
 void spmv_dot(const DCsr &A, const double *x, double *y, const double *w, int slot, const HaloPlan *halo)
 {
-   launch_spmv<MODE_PLAIN, true>(A, halo, x, 1.0, 0.0, nullptr, nullptr, nullptr, w, y, Context::get().slot(slot));
+   SpmvCall c(x, y);
+   c.w       = w;
+   c.partial = Context::get().slot(slot);
+   launch_spmv<MODE_PLAIN, true>(A, halo, c);
 }
 void residual(const DCsr &A, const double *x, const double *b, double *out, const HaloPlan *halo)
 {
-   launch_spmv<MODE_RESID, false>(A, halo, x, 1.0, 0.0, nullptr, b, nullptr, nullptr, out, nullptr);
+   SpmvCall c(x, out);
+   c.b = b;
+   launch_spmv<MODE_RESID, false>(A, halo, c);
 }
 void jacobi(const DCsr &A, const double *dinv, const double *b, const double *x_in, double *x_out, int dot_slot, const HaloPlan *halo)
 {
+   SpmvCall c(x_in, x_out);
+   c.b    = b;
+   c.dinv = dinv;
    if (dot_slot >= 0)
-      launch_spmv<MODE_JACOBI, true>(A, halo, x_in, 1.0, 0.0, nullptr, b, dinv, nullptr, x_out, Context::get().slot(dot_slot));
-   else
-      launch_spmv<MODE_JACOBI, false>(A, halo, x_in, 1.0, 0.0, nullptr, b, dinv, nullptr, x_out, nullptr);
+   {
+      c.partial = Context::get().slot(dot_slot);
+      launch_spmv<MODE_JACOBI, true>(A, halo, c);
+   }
+   else launch_spmv<MODE_JACOBI, false>(A, halo, c);
 }
 
-namespace {
-struct FoldArmed { // disarmed on every way out, like EpilogueArmed
-   explicit FoldArmed(const DCsr *M) { g_fold = SpmvFold{M, false}; }
-   ~FoldArmed() { g_fold = SpmvFold{}; }
-};
-} // namespace
 bool spmv_foldable(const DCsr &Pt)
 {
    if (Pt.nrows == 0 || Pt.nnz == 0) return false;
@@ -2629,9 +2558,13 @@ bool spmv_foldable(const DCsr &Pt)
 void jacobi_folded(const DCsr &A, const DCsr &Pt, const double *dinv, const double *t, const double *e, const double *u, double *out)
 {
    HDA_REQUIRE(Pt.nrows == A.nrows, "folded sweep: P~ has the rows of the level's operator");
-   FoldArmed armed(&Pt);
-   launch_spmv<MODE_JACOBI, false>(A, nullptr, e, 1.0, 0.0, u, t, dinv, nullptr, out, nullptr);
-   HDA_REQUIRE(g_fold.done, "folded sweep: the launch did not take the fold");
+   SpmvCall c(e, out);
+   c.yin  = u;
+   c.b    = t;
+   c.dinv = dinv;
+   c.fold = &Pt;
+   const bool taken = launch_spmv<MODE_JACOBI, false>(A, nullptr, c);
+   HDA_REQUIRE(taken, "folded sweep: the launch did not take the fold");
 }
 
 // ---- test entries of the product family (hda_csr_form, hda_spmv_mode)
@@ -2674,21 +2607,36 @@ void spmv_test_mode(const DCsr &A, int mode, int nown, double alpha, double beta
    else
    { // the split product of launch_spmv_halo, with every column of x in place
       ensure_offd(A, nown);
-      double    *part = Context::get().slot(slot);
       const auto none = [] {};
+      SpmvCall   c(x, y);
+      if (fused) c.partial = Context::get().slot(slot);
       switch (mode)
       {
-         case SPMV_TEST_PLAIN: launch_spmv_split<MODE_PLAIN, false>(A, nown, x, alpha, beta, yin, nullptr, nullptr, nullptr, y, nullptr, none); break;
-         case SPMV_TEST_PLAIN_DOT: launch_spmv_split<MODE_PLAIN, true>(A, nown, x, 1.0, 0.0, nullptr, nullptr, nullptr, w, y, part, none); break;
-         case SPMV_TEST_RESID: launch_spmv_split<MODE_RESID, false>(A, nown, x, 1.0, 0.0, nullptr, b, nullptr, nullptr, y, nullptr, none); break;
-         case SPMV_TEST_JACOBI: launch_spmv_split<MODE_JACOBI, false>(A, nown, x, 1.0, 0.0, nullptr, b, dinv, nullptr, y, nullptr, none); break;
-         case SPMV_TEST_JACOBI_DOT: launch_spmv_split<MODE_JACOBI, true>(A, nown, x, 1.0, 0.0, nullptr, b, dinv, nullptr, y, part, none); break;
-         default:
-         {
-            EpilogueArmed armed(dinv2, y2);
-            launch_spmv_split<MODE_PLAIN, false>(A, nown, x, 1.0, 0.0, nullptr, nullptr, nullptr, nullptr, y, nullptr, none);
-            *epilogue_taken = g_epilogue.done;
-         }
+         case SPMV_TEST_PLAIN:
+            c.alpha = alpha;
+            c.beta  = beta;
+            c.yin   = yin;
+            launch_spmv_split<MODE_PLAIN, false>(A, nown, c, none);
+            break;
+         case SPMV_TEST_PLAIN_DOT:
+            c.w = w;
+            launch_spmv_split<MODE_PLAIN, true>(A, nown, c, none);
+            break;
+         case SPMV_TEST_RESID:
+            c.b = b;
+            launch_spmv_split<MODE_RESID, false>(A, nown, c, none);
+            break;
+         case SPMV_TEST_JACOBI:
+         case SPMV_TEST_JACOBI_DOT:
+            c.b    = b;
+            c.dinv = dinv;
+            if (fused) launch_spmv_split<MODE_JACOBI, true>(A, nown, c, none);
+            else launch_spmv_split<MODE_JACOBI, false>(A, nown, c, none);
+            break;
+         default: // the second result is offered; the owned-column half of a split product does not take it
+            c.dinv2         = dinv2;
+            c.out2          = y2;
+            *epilogue_taken = launch_spmv_split<MODE_PLAIN, false>(A, nown, c, none);
       }
    }
    if (fused)
