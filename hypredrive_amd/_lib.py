@@ -585,6 +585,23 @@ class Amg:
         _check(load().hda_amg_fold_sweep(self.h, level, _dp(dinv), _dp(t), _dp(e), _dp(u), _dp(out)))
         return out
 
+    def level0_sweep(self, b, x, direction=0, want_dot=False):
+        """One Jacobi sweep on level 0 as the cycle launches it: (x + dinv (b - A x), <b, out> or None, divisors read by row class?)."""
+        b, x = (np.ascontiguousarray(v, dtype=np.float64) for v in (b, x))
+        out, dot, by_class = np.zeros_like(b), C.c_double(), C.c_int()
+        L = load()
+        L.hda_amg_level0_sweep.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                           C.POINTER(C.c_double), C.POINTER(C.c_int)]
+        _check(L.hda_amg_level0_sweep(self.h, direction, _dp(b), _dp(x), _dp(out), C.byref(dot) if want_dot else None, C.byref(by_class)))
+        return out, (dot.value if want_dot else None), bool(by_class.value)
+
+    def rebind(self, A):
+        """Level 0 on another matrix of the same size; divisors and coarse levels are kept (preconditioner reuse)."""
+        L = load()
+        L.hda_amg_rebind.argtypes = [C.c_void_p, C.c_void_p]
+        _check(L.hda_amg_rebind(self.h, A.h))
+        self.A = A
+
     def ilu_factors(self, level):
         """Factors of the complex smoother (amg.smoother.type ilu) of a level."""
         out = C.c_void_p()

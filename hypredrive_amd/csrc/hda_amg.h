@@ -242,6 +242,8 @@ void schwarz_solve(Schwarz &S, const DCsr &A, const double *b, double *x, bool z
 struct FirstSweepFusion {
    bool          valid = false;   // offer: the next application from a zero guess may have its first sweep done by the caller
    const double *dinv  = nullptr; //   divisors of that sweep
+   const unsigned char *rclass = nullptr; // ... and, where the operator is row-class coded and its divisors are one number per class
+   const double *cdinv = nullptr; //   (Amg::class_dinv), the class bytes and the 128-entry table to read in place of dinv[i]
    double       *dest  = nullptr; //   where the sweep's result is expected; nullptr = the application's output vector itself
    int           n     = 0;       //   rows of the operator the offer is about (a caller iterating on another system must not take it)
    const void   *owner = nullptr; //   the preconditioner that made the offer
@@ -271,6 +273,11 @@ struct AmgLevel {
    DArray<int>    cf;
    std::vector<int> blk_part; // row blocks of this level (AmgParams::blocks): V + 1 row starts; empty = one block
    DArray<double> dinv_down, dinv_up; // relax_weight / l1 (or / a_ii), per cycle direction
+   // level 0 on a row-class coded operator: the same divisors as one number per row class, verified row by row
+   // against dinv_down / dinv_up (class_divisors); empty where that failed or does not apply.  cdinv_gen: the operator they were
+   // verified on (DCsr::gen) -- another matrix under kept divisors (Amg::rebind) verifies them again or goes without.
+   DArray<double> cdinv_down, cdinv_up;
+   unsigned long long cdinv_gen = 0;
    DArray<double> dinv_pts[2][2];     // F / C relaxation: [direction 0 down, 1 up][0 F points, 1 C points] -- that direction's divisors, 0 elsewhere
    // two-stage Gauss-Seidel on this level: L bounds, divisors when neither direction's are the plain diagonal (a coarse relaxation of
    // its own), the work vector of z1 (type 12)
@@ -342,6 +349,10 @@ class Amg {
    // algorithmic HBM bytes of one V-cycle (SURVEY 8(d) formulas on the built hierarchy)
    double        vcycle_bytes(bool format = false) const; // format: bytes the kernels read (coded operators), else the CSR figure
    bool          level_folded(int l) const { return l >= 0 && l < num_levels() && levels[(size_t)l].folded; }
+   // seam for the tests of the level-0 divisors by row class: one Jacobi sweep of direction dir (0 down, 1 up) on
+   // level 0 exactly as the cycle launches it, out = x + dinv (b - A x), partials of <b, out> into dot_slot >= 0; the return value
+   // says whether the launch read its divisors from the class table
+   bool          level0_sweep(int dir, const double *b, const double *x, double *out, int dot_slot);
    AmgParams     prm;
    int           blocks_used = 1;      // row blocks the setup worked with (AmgParams::blocks resolved)
    const std::vector<int> &level_blocks(int l) const { return levels[(size_t)l].blk_part; }
@@ -353,6 +364,8 @@ class Amg {
               bool zero_guess, int dot_slot);
    int           sweep_points(int dir, int s) const;    // points of sweep s of direction dir (0 down, 1 up): 0 all, -1 F, 1 C
    const double *sweep_dinv(int l, int dir, int s);     // divisors of that sweep on level l (masked for F / C sweeps)
+   void          build_class_dinv();                    // level 0: cdinv_down / cdinv_up from the divisors in place, verified
+   const double *class_dinv(int l, const double *dinv); // the class table that stands for these divisors, or null (HDA_CLASS_DINV=0: null)
    void          check_air_params() const;              // restriction_type / relaxation points: refusal by name of what is not built
    bool          needs_cf_in_cycle() const;             // some sweep relaxes F or C points only
    void build_hierarchy(const DCsr &A, bool keep_ap = false); // keep_ap: levels >= 1 keep A_l P_l in AmgLevel::Pt (fold_level)

@@ -2971,6 +2971,42 @@ int amg_auto_blocks(const DCsr &A)
    return (int)std::max(1LL, std::min(1024LL, (long long)n / m));
 }
 
+// Level 0, one rank, one row block: the Jacobi divisors as one number per row class.  l1 norm and diagonal
+// depend on the values of the row alone, and a row's class is its sequence of (value, offset) codes, so rows of a class share a
+// divisor -- which class_divisors does not take on trust: it compares every row's divisor with its class's entry, bit for bit, and
+// one mismatch leaves the table out.  Divisors of a point set (F / C relaxation) live in arrays of their own and never get a table.
+void Amg::build_class_dinv()
+{
+   AmgLevel &lv = levels[0];
+   lv.cdinv_down.release();
+   lv.cdinv_up.release();
+   const DCsr &A = level_A(0);
+   lv.cdinv_gen  = A.gen;
+   if (dist || blocks_used > 1 || lv.blk_part.size() > 2 || !lv.dinv_down.size()) return; // (row blocks: the divisors may depend on the block)
+   class_divisors(A, lv.dinv_down.data(), lv.cdinv_down);
+   if (!same_divisors(prm.relax_up, prm.relax_down) && lv.dinv_up.size()) class_divisors(A, lv.dinv_up.data(), lv.cdinv_up);
+}
+const double *Amg::class_dinv(int l, const double *dinv)
+{
+   if (l != 0 || !dinv) return nullptr;
+   const char *e = getenv("HDA_CLASS_DINV"); // (read per call, as HDA_FOLD_UP: the tests switch it inside one process)
+   if (e && atoi(e) == 0) return nullptr;
+   AmgLevel &lv = levels[0];
+   if (lv.cdinv_gen != level_A(0).gen) return nullptr; // not the operator the tables were verified on
+   if (dinv == lv.dinv_down.data() && lv.cdinv_down.size()) return lv.cdinv_down.data();
+   if (dinv == lv.dinv_up.data() && lv.cdinv_up.size()) return lv.cdinv_up.data();
+   return nullptr;
+}
+
+bool Amg::level0_sweep(int dir, const double *b, const double *x, double *out, int dot_slot)
+{
+   HDA_REQUIRE(num_levels() > 1 && is_jacobi_type(dir == 0 ? prm.relax_down : prm.relax_up) && !levels[0].ilu && !dist,
+               "level0_sweep: level 0 of this hierarchy is not relaxed by a Jacobi sweep on one rank");
+   const double *dinv = sweep_dinv(0, dir, 0), *cd = class_dinv(0, dinv);
+   jacobi(level_A(0), dinv, b, x, out, dot_slot, nullptr, cd);
+   return cd != nullptr && row_classes(level_A(0)) != nullptr;
+}
+
 void Amg::build_smoother_data(int l)
 {
    const DCsr &Al = level_A(l);
@@ -2994,6 +3030,7 @@ void Amg::build_smoother_data(int l)
       else build_dinv(Al, prm.relax_up, prm.relax_weight, lv.dinv_up);
       if (gs && !lv.gs.built) build_gs_plan(Al, lv.gs);
    }
+   if (l == 0) build_class_dinv();
    if (!last)
    { // F / C relaxation (relaxation.points): the divisors of such a sweep, zero outside its point set
       for (int dir = 0; dir < 2; dir++)
@@ -3410,6 +3447,7 @@ void Amg::rebind(const DCsr &A, const HaloPlan *hA)
    a0_dims[0] = A.nrows; a0_dims[1] = A.ncols; a0_dims[2] = A.nnz;
    if (dist) hA0 = hA;
    spmv_prepare(A);
+   build_class_dinv(); // the kept divisors against THIS matrix's row classes: verified again, or read from the vector
 }
 
 __global__ __launch_bounds__(256) void k_cmark(int n, const int *__restrict__ cf, int *__restrict__ m)
@@ -3622,6 +3660,16 @@ double Amg::vcycle_bytes(bool format) const
          s += 24.0 * n;                                            // zero-guess sweep: dinv, f -> u
          s += (prm.sweeps_down - 1) * (spmv_bytes(A, format) + 16.0 * n);  // further pre-sweeps
          s += (prm.sweeps_up - (levels[l].folded ? 1 : 0)) * (spmv_bytes(A, format) + 16.0 * n); // post-sweeps (a folded level: all but the first)
+         const char *cde = getenv("HDA_CLASS_DINV");
+         if (format && l == 0 && !(cde && atoi(cde) == 0) && levels[0].cdinv_gen == A.gen && !needs_cf_in_cycle())
+         { // divisors by row class: a class byte the sweep reads anyway in place of 8 bytes per row; the zero-guess
+           // sweep (the update kernel's, or jacobi_zero_guess, which keeps reading the vector: counted as the fused form) reads 1 for 8
+            const AmgLevel &l0 = levels[0];
+            const bool dn = is_jacobi_type(prm.relax_down) && l0.cdinv_down.size();
+            const bool up = is_jacobi_type(prm.relax_up) && (same_divisors(prm.relax_up, prm.relax_down) ? l0.cdinv_down.size() : l0.cdinv_up.size());
+            if (dn && prm.sweeps_down >= 1) s -= 7.0 * n + (prm.sweeps_down - 1) * 8.0 * n;
+            if (up) s -= prm.sweeps_up * 8.0 * n;
+         }
       }
       s += spmv_bytes(A, format) + 8.0 * n;                             // residual
       s += spmv_bytes(levels[l].R, format);                             // restriction
@@ -3931,7 +3979,7 @@ void Amg::relax(int l, int type, const double *dinv, const double *b, double *&c
    }
    else
    {
-      jacobi(A, dinv, b, cur, alt, dot_slot, fresh ? nullptr : &level_hA(l)); // ghost refresh of cur runs under the sweep's owned-column part
+      jacobi(A, dinv, b, cur, alt, dot_slot, fresh ? nullptr : &level_hA(l), class_dinv(l, dinv)); // ghost refresh of cur runs under the sweep's owned-column part
       std::swap(cur, alt);
    }
 }
@@ -3991,6 +4039,8 @@ void Amg::apply_offering(const double *b, double *x, int dot_slot)
    {
       double *d = first_sweep_dest(x);
       fs.dinv   = sweep_dinv(0, 0, 0);
+      fs.cdinv  = class_dinv(0, fs.dinv);
+      fs.rclass = fs.cdinv ? row_classes(level_A(0)) : nullptr;
       fs.dest   = (d == x) ? nullptr : d;
       fs.n      = level_A(0).nrows;
       fs.owner  = this;

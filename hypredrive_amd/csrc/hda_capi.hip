@@ -1098,6 +1098,34 @@ extern "C" int hda_amg_fold_sweep(hda_amg_t h, int level, const double *dinv, co
    dout.download(out, (size_t)M.nrows);
    HDA_CATCH
 }
+// one level-0 Jacobi sweep as the cycle launches it (Amg::level0_sweep); *dot (may be null): <b, out> from the sweep's fused partials;
+// *by_class: whether the divisors came from the row-class table
+extern "C" int hda_amg_level0_sweep(hda_amg_t h, int dir, const double *b, const double *x, double *out, double *dot, int *by_class)
+{
+   HDA_TRY
+   HDA_REQUIRE(h && h->amg && b && x && out && by_class, "hda_amg_level0_sweep: null argument");
+   const DCsr    &A = h->amg->level_A(0);
+   DArray<double> db, dx((size_t)std::max(A.ncols, A.nrows)), dout((size_t)A.nrows);
+   db.upload(b, (size_t)A.nrows);
+   dx.zero();
+   dx.upload(x, (size_t)A.nrows);
+   *by_class = h->amg->level0_sweep(dir, db.data(), dx.data(), dout.data(), dot ? 0 : -1) ? 1 : 0;
+   if (dot)
+   {
+      finalize(0, S_TMP);
+      *dot = read_scalar(S_TMP);
+   }
+   dout.download(out, (size_t)A.nrows);
+   HDA_CATCH
+}
+// the hierarchy's level 0 on another matrix of the same size, divisors and coarse levels kept (Amg::rebind: preconditioner reuse)
+extern "C" int hda_amg_rebind(hda_amg_t h, hda_csr_t A)
+{
+   HDA_TRY
+   HDA_REQUIRE(h && h->amg && A, "hda_amg_rebind: null argument");
+   h->amg->rebind(A->get(), nullptr);
+   HDA_CATCH
+}
 extern "C" int hda_amg_level_cf(hda_amg_t h, int level, int *cf)
 {
    HDA_TRY

@@ -17,10 +17,27 @@ struct hypre_IJVector_struct {
    size_t               capacity = 0; // doubles available behind data()
    double              *view = nullptr; // non-owning alias of somebody else's HBM buffer
    std::vector<double>  host_mirror; // backing store for "get values" pointers
-   double              *data() { return view ? view : d.data(); }
-   const double        *data() const { return view ? view : d.data(); }
+   // Modification counter.  Everything that can change the values bumps it: the mutable accessor data() (whoever takes it may
+   // write), the value setters, Assemble, a fill or a copy into the vector, and handing the handle to a caller
+   // (HYPREDRV_LinearSystemGetSolution / GetRHS).  The library's read paths take cdata(), which leaves it alone.  Two facts are
+   // kept per counter value and are void as soon as it moves:
+   //   zero_at: the vector was filled by the library's own zero fill (or copied from a vector in that state) and nothing has
+   //            written it since -- x = 0 exactly, so b - A x is b bit for bit
+   //   bb_at:   <v,v> as the dot kernel and its finalize computed it (bb), so that r0, PCG's bi_prod and the relative residual of
+   //            one solve share one reduction and one read-back
+   unsigned long long   version = 1, zero_at = 0, bb_at = 0;
+   double               bb = 0.0;
+   void                 touch() { version++; }
+   void                 mark_zero() { zero_at = version; }
+   bool                 known_zero() const { return zero_at == version && stage.empty() && nloc > 0; }
+   double              *data() { touch(); return view ? view : d.data(); }
+   const double        *cdata() const { return view ? view : d.data(); }
    void                 ensure_device();
 };
+namespace hda {
+bool   known_zero_enabled();                        // HDA_KNOWN_ZERO (default on), read per call
+double vector_self_dot(hypre_IJVector_struct *v);   // <v,v>: cached per (vector, version) when the switch is on
+} // namespace hda
 
 struct hypre_IJMatrix_struct {
    MPI_Comm  comm = MPI_COMM_WORLD;

@@ -86,8 +86,34 @@ void hypre_IJVector_struct::ensure_device()
       d.alloc((size_t)std::max(nloc, 1));
       d.zero();
       capacity = d.size();
+      touch();
    }
 }
+
+namespace hda {
+bool known_zero_enabled()
+{
+   // One rank only: the counters are per rank, and a rank that skips a reduction or a halo refresh its neighbours still run
+   // would leave them waiting (a caller may well set values on one rank's rows alone).
+   if (Comm::world().size > 1) return false;
+   const char *e = getenv("HDA_KNOWN_ZERO"); // (read per call: the tests switch it inside one process)
+   return !(e && atoi(e) == 0);
+}
+double vector_self_dot(hypre_IJVector_struct *v)
+{
+   const bool cache = known_zero_enabled();
+   if (cache && v->bb_at == v->version) return v->bb;
+   dot(v->nloc, v->cdata(), v->cdata(), 0);
+   finalize(0, S_TMP);
+   const double bb = read_scalar(S_TMP);
+   if (cache)
+   {
+      v->bb    = bb;
+      v->bb_at = v->version;
+   }
+   return bb;
+}
+} // namespace hda
 
 extern "C" HYPRE_Int HYPRE_IJVectorCreate(MPI_Comm comm, HYPRE_BigInt jlower, HYPRE_BigInt jupper, HYPRE_IJVector *vector)
 {
@@ -115,6 +141,7 @@ extern "C" HYPRE_Int HYPRE_IJVectorInitialize_v2(HYPRE_IJVector v, HYPRE_MemoryL
 {
    HY_TRY
    v->stage.assign((size_t)v->nloc, 0.0);
+   v->touch();
    v->initialized = true;
    v->assembled   = false;
    HY_CATCH
@@ -128,8 +155,9 @@ static HYPRE_Int vec_set(HYPRE_IJVector v, HYPRE_Int n, const HYPRE_BigInt *idx,
    if (v->assembled && v->stage.empty())
    { // re-open an assembled vector: pull the device values back into the stage
       v->stage.resize((size_t)v->nloc);
-      download_sync(v->stage.data(), v->data(), sizeof(double) * (size_t)v->nloc);
+      download_sync(v->stage.data(), v->cdata(), sizeof(double) * (size_t)v->nloc);
    }
+   v->touch();
    for (int q = 0; q < n; q++)
    {
       const long long l = idx ? idx[q] - v->jlower : q;
@@ -152,6 +180,7 @@ extern "C" HYPRE_Int HYPRE_IJVectorAssemble(HYPRE_IJVector v)
 {
    HY_NEED_DEVICE;
    HY_TRY
+   v->touch();
    if (!v->stage.empty() || v->nloc == 0)
    {
       v->d.alloc((size_t)std::max(v->nloc, 1));
@@ -171,7 +200,7 @@ extern "C" HYPRE_Int HYPRE_IJVectorGetValues(HYPRE_IJVector v, HYPRE_Int n, cons
    else
    {
       h.resize((size_t)std::max(v->nloc, 1));
-      download_sync(h.data(), v->data(), sizeof(double) * (size_t)v->nloc);
+      download_sync(h.data(), v->cdata(), sizeof(double) * (size_t)v->nloc);
       src = h.data();
    }
    for (int q = 0; q < n; q++)
@@ -250,6 +279,7 @@ extern "C" HYPRE_Int HYPRE_IJVectorRead(const char *filename, MPI_Comm comm, HYP
    HYPRE_IJVectorCreate(comm, lo, hi, vector);
    HYPRE_IJVectorInitialize(*vector);
    for (auto &e : ent) (*vector)->stage[(size_t)(e.first - lo)] = e.second;
+   (*vector)->touch();
    return HYPRE_IJVectorAssemble(*vector);
    HY_CATCH
 }
@@ -332,6 +362,7 @@ extern "C" HYPRE_Int hda_IJVectorReadMultipartBinary(const char *prefix, MPI_Com
    HYPRE_IJVectorCreate(comm, lo, lo + (long long)vals.size() - 1, vector);
    HYPRE_IJVectorInitialize(*vector);
    std::copy(vals.begin(), vals.end(), (*vector)->stage.begin());
+   (*vector)->touch();
    return HYPRE_IJVectorAssemble(*vector);
    HY_CATCH
 }
@@ -896,23 +927,25 @@ extern "C" HYPRE_Int HYPRE_ParCSRMatrixMatvec(HYPRE_Complex alpha, HYPRE_ParCSRM
    HY_NEED_DEVICE;
    HY_TRY
    HDA_REQUIRE(A && A->assembled && x && y, "Matvec needs assembled operands");
-   const double  *xin = x->data();
+   const double  *xin = x->cdata();
    DArray<double> xe;
    if (A->A.ncols > A->nloc || x->capacity < (size_t)A->A.ncols)
    { // stage x into an extended vector and refresh the ghost tail
       xe.alloc((size_t)std::max(A->A.ncols, 1));
-      copy(A->nloc, x->data(), xe.data());
+      copy(A->nloc, x->cdata(), xe.data());
       halo_exchange(A->halo, xe.data());
       xin = xe.data();
    }
-   spmv(A->A, alpha, xin, beta, y->data(), y->data());
+   double *yd = y->data();
+   spmv(A->A, alpha, xin, beta, yd, yd);
    HY_CATCH
 }
 extern "C" HYPRE_Int HYPRE_ParVectorInnerProd(HYPRE_ParVector x, HYPRE_ParVector y, HYPRE_Real *prod)
 {
    HY_NEED_DEVICE;
    HY_TRY
-   dot(x->nloc, x->data(), y->data(), 0);
+   if (x == y) { *prod = vector_self_dot(x); return 0; } // (one reduction per vector state: hda_hypre.h)
+   dot(x->nloc, x->cdata(), y->cdata(), 0);
    finalize(0, S_TMP);
    *prod = read_scalar(S_TMP);
    HY_CATCH
@@ -929,7 +962,8 @@ extern "C" HYPRE_Int HYPRE_ParVectorCopy(HYPRE_ParVector x, HYPRE_ParVector y)
 {
    HY_TRY
    y->ensure_device();
-   copy(x->nloc, x->data(), y->data());
+   copy(x->nloc, x->cdata(), y->data());
+   if (x->known_zero() && x->nloc == y->nloc && y->stage.empty()) y->mark_zero();
    HY_CATCH
 }
 extern "C" HYPRE_Int HYPRE_ParVectorScale(HYPRE_Complex a, HYPRE_ParVector x)
@@ -941,7 +975,7 @@ extern "C" HYPRE_Int HYPRE_ParVectorScale(HYPRE_Complex a, HYPRE_ParVector x)
 extern "C" HYPRE_Int HYPRE_ParVectorAxpy(HYPRE_Complex a, HYPRE_ParVector x, HYPRE_ParVector y)
 {
    HY_TRY
-   axpy(x->nloc, a, x->data(), y->data());
+   axpy(x->nloc, a, x->cdata(), y->data());
    HY_CATCH
 }
 extern "C" HYPRE_Int HYPRE_ParVectorSetConstantValues(HYPRE_ParVector v, HYPRE_Complex value)
@@ -951,6 +985,7 @@ extern "C" HYPRE_Int HYPRE_ParVectorSetConstantValues(HYPRE_ParVector v, HYPRE_C
    v->ensure_device();
    std::vector<double>().swap(v->stage);
    fill(v->nloc, value, v->data());
+   if (value == 0.0 && !std::signbit(value)) v->mark_zero();
    v->assembled = true;
    HY_CATCH
 }
@@ -1121,10 +1156,20 @@ static HYPRE_Int krylov_solve(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVec
          if (slot >= 0 && !done) dot(n, r, z, slot);
       };
    }
-   s->last = (s->kind == HDA_SOLVER_GMRES)      ? gmres(op, M, s->kp, b->data(), x->data())
-             : (s->kind == HDA_SOLVER_FGMRES)   ? fgmres(op, M, s->kp, b->data(), x->data())
-             : (s->kind == HDA_SOLVER_BICGSTAB) ? bicgstab(op, M, s->kp, b->data(), x->data())
-                                                : pcg(op, M, s->kp, b->data(), x->data());
+   // what the vectors' counters know (hda_hypre.h), taken before x is handed over for writing: PCG starts from r = b when x is the
+   // library's untouched zero fill, and shares <b,b> with the driver's r0 and relative residual
+   PcgKnown known;
+   if (s->kind == HDA_SOLVER_PCG && known_zero_enabled())
+   {
+      known.x_zero = x->known_zero() && x != b;
+      if (s->kp.two_norm) known.bb = vector_self_dot(b);
+   }
+   const double *bd = b->cdata();
+   double       *xd = x->data();
+   s->last = (s->kind == HDA_SOLVER_GMRES)      ? gmres(op, M, s->kp, bd, xd)
+             : (s->kind == HDA_SOLVER_FGMRES)   ? fgmres(op, M, s->kp, bd, xd)
+             : (s->kind == HDA_SOLVER_BICGSTAB) ? bicgstab(op, M, s->kp, bd, xd)
+                                                : pcg(op, M, s->kp, bd, xd, &known);
    if (!s->last.converged) g_hcode |= HYPRE_ERROR_CONV; // soft error, as in hypre
    HY_CATCH
 }

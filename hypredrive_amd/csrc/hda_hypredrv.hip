@@ -1075,7 +1075,7 @@ extern "C" uint32_t HYPREDRV_LinearSystemGetSolutionValues(HYPREDRV_t h, HYPRE_C
    if (!h->vec_x || !data) return err_set(ERR_UNKNOWN, "no solution vector");
    HYPRE_IJVector x = h->vec_x;
    x->host_mirror.resize((size_t)std::max(x->nloc, 1));
-   download_sync(x->host_mirror.data(), x->data(), sizeof(double) * (size_t)x->nloc);
+   download_sync(x->host_mirror.data(), x->cdata(), sizeof(double) * (size_t)x->nloc);
    *data = x->host_mirror.data();
    API_CATCH
 }
@@ -1086,7 +1086,7 @@ extern "C" uint32_t HYPREDRV_LinearSystemGetRHSValues(HYPREDRV_t h, HYPRE_Comple
    if (!h->vec_b || !data) return err_set(ERR_UNKNOWN, "no right-hand side");
    HYPRE_IJVector b = h->vec_b;
    b->host_mirror.resize((size_t)std::max(b->nloc, 1));
-   download_sync(b->host_mirror.data(), b->data(), sizeof(double) * (size_t)b->nloc);
+   download_sync(b->host_mirror.data(), b->cdata(), sizeof(double) * (size_t)b->nloc);
    *data = b->host_mirror.data();
    API_CATCH
 }
@@ -1143,8 +1143,9 @@ extern "C" uint32_t HYPREDRV_LinearSystemGetSolutionNorm(HYPREDRV_t h, const cha
    consume_hypre_errors();
    API_CATCH
 }
-extern "C" uint32_t HYPREDRV_LinearSystemGetSolution(HYPREDRV_t h, HYPRE_Vector *vec) { CHECK_INIT_OBJ(h); *vec = h->vec_x; return g_err; }
-extern "C" uint32_t HYPREDRV_LinearSystemGetRHS(HYPREDRV_t h, HYPRE_Vector *vec) { CHECK_INIT_OBJ(h); *vec = h->vec_b; return g_err; }
+// (the handle leaves the library: whatever was known about the values -- hda_hypre.h -- is no longer relied on)
+extern "C" uint32_t HYPREDRV_LinearSystemGetSolution(HYPREDRV_t h, HYPRE_Vector *vec) { CHECK_INIT_OBJ(h); *vec = h->vec_x; if (h->vec_x) h->vec_x->touch(); return g_err; }
+extern "C" uint32_t HYPREDRV_LinearSystemGetRHS(HYPREDRV_t h, HYPRE_Vector *vec) { CHECK_INIT_OBJ(h); *vec = h->vec_b; if (h->vec_b) h->vec_b->touch(); return g_err; }
 extern "C" uint32_t HYPREDRV_LinearSystemGetMatrix(HYPREDRV_t h, HYPRE_Matrix *mat) { CHECK_INIT_OBJ(h); *mat = h->mat_A; return g_err; }
 
 extern "C" uint32_t HYPREDRV_LinearSystemPrint(HYPREDRV_t h)
@@ -1306,7 +1307,7 @@ static void project_out_null_space(hypredrv_struct *h)
    HDA_REQUIRE(h->num_ns <= Context::kNumSlots && S_GMRES + h->num_ns <= Context::kNumScalars, "too many null space modes for the reduction scratch");
    h->vec_x->ensure_device();
    const int n = h->ns_nloc;
-   for (int k = 0; k < h->num_ns; k++) dot(n, h->vec_x->data(), h->ns_modes.data() + (size_t)k * (size_t)n, k);
+   for (int k = 0; k < h->num_ns; k++) dot(n, h->vec_x->cdata(), h->ns_modes.data() + (size_t)k * (size_t)n, k);
    finalize_n(0, h->num_ns, S_GMRES);
    for (int k = 0; k < h->num_ns; k++) axpy_dev(n, S_GMRES + k, -1.0, h->ns_modes.data() + (size_t)k * (size_t)n, h->vec_x->data());
 }
@@ -1367,7 +1368,7 @@ extern "C" uint32_t HYPREDRV_StateVectorApplyCorrection(HYPREDRV_t h, int state_
    if (!v) return err_set(ERR_INVALID_VAL, "StateVectorApplyCorrection: index outside the states set with StateVectorSet");
    if (!h->vec_x || h->vec_x->nloc != v->nloc) return err_set(ERR_UNKNOWN, "StateVectorApplyCorrection: no solution vector of matching size");
    std::vector<double> dx((size_t)std::max(v->nloc, 1));
-   download_sync(dx.data(), h->vec_x->data(), sizeof(double) * (size_t)v->nloc);
+   download_sync(dx.data(), h->vec_x->cdata(), sizeof(double) * (size_t)v->nloc);
    for (int i = 0; i < v->nloc; i++) v->stage[(size_t)i] += dx[(size_t)i];
    API_CATCH
 }
@@ -1538,6 +1539,14 @@ extern "C" int hda_amd_hierarchy_levels(void *obj) // partitioned levels + the l
 // bytes THIS rank streams per Krylov iteration (operator product + vector updates) and per
 // V-cycle with the hierarchy that was set up: [0] CSR figures of SURVEY 8(d), [1] the formats
 // actually read (coded operators).  bench.py sums them over the ranks.
+extern "C" uint32_t HYPREDRV_AMD_LastResidualNorms(HYPREDRV_t h, double *r0, double *rel, int *x_known_zero)
+{
+   CHECK_INIT_OBJ(h);
+   if (r0) *r0 = h->stats.cur().r0;
+   if (rel) *rel = h->stats.cur().rr;
+   if (x_known_zero) *x_known_zero = (h->vec_x && known_zero_enabled() && h->vec_x->known_zero()) ? 1 : 0;
+   return g_err;
+}
 extern "C" uint32_t HYPREDRV_AMD_SolvePhaseBytes(HYPREDRV_t h, double iteration[2], double vcycle[2])
 {
    CHECK_INIT_OBJ(h);
@@ -2347,22 +2356,24 @@ extern "C" uint32_t HYPREDRV_LinearSolverSetup(HYPREDRV_t h)
 }
 
 // ||b - A x||_2 (reference src/internal/linsys.c:2982-3067): the residual kernel on a work vector from the library's pool,
-// the ghost refresh of x under it on a row block
+// the ghost refresh of x under it on a row block.  While x is the library's untouched zero fill (hda_hypre.h; HDA_KNOWN_ZERO=0
+// switches it off) the residual is b bit for bit, and its norm is the cached <b,b> of the same dot kernel.
 static double residual_norm(hypredrv_struct *h)
 {
    hypre_IJMatrix_struct *A = h->mat_A;
    const int              n = A->nloc;
    h->vec_x->ensure_device();
    h->vec_b->ensure_device();
+   if (known_zero_enabled() && h->vec_x->known_zero() && h->vec_x->nloc == n && h->vec_b->nloc == n) return std::sqrt(vector_self_dot(h->vec_b));
    DArray<double> r((size_t)std::max(n, 1)), xe;
-   double        *xin = h->vec_x->data();
+   const double  *xin = h->vec_x->cdata();
    if (A->A.ncols > n || h->vec_x->capacity < (size_t)A->A.ncols)
    { // x has no room for the ghost tail: stage it
       xe.alloc((size_t)std::max(A->A.ncols, 1));
-      copy(n, h->vec_x->data(), xe.data());
+      copy(n, h->vec_x->cdata(), xe.data());
       xin = xe.data();
    }
-   residual(A->A, xin, h->vec_b->data(), r.data(), Comm::world().size > 1 ? &A->halo : nullptr);
+   residual(A->A, xin, h->vec_b->cdata(), r.data(), Comm::world().size > 1 ? &A->halo : nullptr);
    dot(n, r.data(), r.data(), 0);
    finalize(0, S_TMP);
    return std::sqrt(read_scalar(S_TMP));
@@ -2420,7 +2431,7 @@ extern "C" uint32_t HYPREDRV_LinearSolverApply(HYPREDRV_t h)
       HYPRE_ParVectorInnerProd(h->vec_xref, h->vec_xref, &rr);
       HYPRE_IJVector e = new_vector_like(h, 0.0);
       HYPRE_ParVectorCopy(h->vec_xref, e);
-      axpy(e->nloc, -1.0, h->vec_x->data(), e->data());
+      axpy(e->nloc, -1.0, h->vec_x->cdata(), e->data());
       HYPRE_ParVectorInnerProd(e, e, &ee);
       HYPRE_IJVectorDestroy(e);
       if (!h->mypid)

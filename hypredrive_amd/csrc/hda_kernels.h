@@ -30,8 +30,16 @@ void residual(const DCsr &A, const double *x, const double *b, double *out, cons
 // ---- K2: l1-Jacobi / weighted Jacobi sweep (hypre_BoomerAMGRelax types 18 / 0,7;
 // selected by src/internal/amg.c:183-186,360-375).  dinv = weight / l1 (or / a_ii).
 // x_out = x_in + dinv .* (b - A*x_in).  dot_slot >= 0 also emits partials of <b, x_out>.
+// cdinv: the same divisors by row class (class_divisors), read instead of dinv[r] where A is row-class coded; null: dinv alone.
 void jacobi(const DCsr &A, const double *dinv, const double *b, const double *x_in,
-            double *x_out, int dot_slot, const HaloPlan *halo = nullptr);
+            double *x_out, int dot_slot, const HaloPlan *halo = nullptr, const double *cdinv = nullptr);
+// Divisors by row class.  The class of a row of a row-class coded operator (DCsr::rclass < 128) is its sequence of (value, offset)
+// codes, so a divisor that depends on the row's values alone -- weight / l1 norm, weight / a_ii -- is one number per class.  Fills
+// table (128 entries) from dinv and verifies it with a pass over all rows: every row with a class below 128 must hold exactly the
+// bit pattern of its class's entry.  false (table released): A is not row-class coded, or one row differs -- masked or
+// block-dependent divisors, divisors kept from another matrix.
+bool class_divisors(const DCsr &A, const double *dinv, DArray<double> &table);
+const unsigned char *row_classes(const DCsr &A); // the class bytes of a row-class coded operator, null otherwise
 // The same sweep right after a prolongation, folded.  With t = b - A u left by the down leg and e the coarse
 // correction, u + P e followed by one Jacobi sweep is out = (u + dinv .* t) + Pt e, Pt = P - diag(dinv) (A P): one pass over Pt in place
 // of a pass over P and a pass over A.  Launched as the Jacobi sweep of A (timing probes on (A, Jacobi) see it); out must not alias u.
@@ -54,11 +62,16 @@ void finalize(int slot, int scalar_idx);                                  // sca
 void finalize_n(int first_slot, int nslots, int first_scalar);            // several at once
 // alpha = gamma/S_SP; x += alpha p; r -= alpha s; partials <r,r>.  sp_slot >= 0 (one rank): <s,p> is finished from that slot of block
 // partials inside the kernel (no finalize launch; same bits).  z0 != null: also z0 = dinv0 .* r (the zero-guess first sweep of the cycle)
+// x == null: the term alpha p is left to the next cg_direction (or cg_flush_x), which reads p anyway; S_SP and gamma stay as they are until then
+// rclass, cdinv (with z0): the divisor of row i is cdinv[rclass[i]] where the class is below 128 (class_divisors), dinv0[i] otherwise
 void cg_update(int n, int gamma_idx, const double *p, const double *s, double *x, double *r, int rr_slot, int sp_slot = -1,
-               const double *dinv0 = nullptr, double *z0 = nullptr);
+               const double *dinv0 = nullptr, double *z0 = nullptr, const unsigned char *rclass = nullptr, const double *cdinv = nullptr);
 // p = z + (gamma_new / gamma_old) p.  first_slot >= 0 (one rank): gamma_new and the scalar after it are finished here from the block
-// partials of slots first_slot, first_slot + 1 (no finalize launch; same bits)
-void cg_direction(int n, int gamma_old_idx, int gamma_new_idx, const double *z, double *p, int first_slot = -1);
+// partials of slots first_slot, first_slot + 1 (no finalize launch; same bits).  x != null: the term a cg_update without x left behind
+// is added first, x += (gamma_old / S_SP) p -- the update kernel's own quotient of the same two scalars, so the same bits
+void cg_direction(int n, int gamma_old_idx, int gamma_new_idx, const double *z, double *p, int first_slot = -1, double *x = nullptr);
+// x += (gamma / S_SP) p alone: the outstanding term of a cg_update without x when the loop ends before its direction step
+void cg_flush_x(int n, int gamma_idx, const double *p, double *x);
 // one step of the single-reduction (Chronopoulos-Gear) PCG: p = u + beta p; s = w + beta s; x += alpha p; r -= alpha s; partials <r,r>
 // with beta, alpha formed on the device from scalars[t_new] = <r,u>, [t_new + 2] = <w,u>, [t_old] = the previous <r,u>, [alpha_idx]
 void cg_single_step(int n, int t_new, int t_old, int alpha_idx, bool first, const double *u, const double *w, double *p, double *s, double *x,

@@ -1123,21 +1123,28 @@ __global__ __launch_bounds__(256) void k_spmv_coded_row(int nrows, const int *__
 // Row-per-lane product of a row-class coded operator: the lane reads its class byte (neighbouring lanes, neighbouring
 // bytes), takes the row's offsets and values from the class table in LDS (lanes of a wave mostly share a class: LDS
 // broadcasts) and keeps the row's <= 8 gathers in flight; x[r + offset] of 64 consecutive rows is a coalesced load.
-template <int MODE, bool DOT, bool SPLIT>
+// CD (MODE_JACOBI): the divisor of a row with a class below 128 comes from cdinv, the 128-entry table of its class's divisor
+// (class_divisors below: rows of one class hold the same values, so their l1 norm or diagonal is the same number), kept in LDS beside
+// the class table; only the CSR rows (class 255) still read dinv[r].  One vector operand less per row: the sweep moves 3 V, not 4.
+template <int MODE, bool DOT, bool SPLIT, bool CD = false>
 __global__ __launch_bounds__(256) void k_spmv_rowclass(int nrows, const unsigned char *__restrict__ rclass,
                                                        const unsigned long long *__restrict__ rc_keys, const double *__restrict__ dval,
                                                        const int *__restrict__ ddelta, const int *__restrict__ rowptr,
                                                        const int *__restrict__ col, const double *__restrict__ val,
                                                        const double *__restrict__ x, double alpha, double beta, const double *yin,
                                                        const double *__restrict__ b, const double *__restrict__ dinv,
-                                                       const double *__restrict__ w, double *out, double *__restrict__ partial, int nown)
+                                                       const double *__restrict__ w, double *out, double *__restrict__ partial, int nown,
+                                                       const double *__restrict__ cdinv = nullptr)
 {
+   static_assert(!CD || MODE == MODE_JACOBI, "class divisors belong to the Jacobi sweep");
    __shared__ double sv[128 * 8];
    __shared__ int    sd[128 * 8];
    __shared__ int    sn[128];
+   __shared__ double sdv[CD ? 128 : 1];
    const int tid = threadIdx.x;
    if (tid < 128)
    {
+      if (CD) sdv[tid] = cdinv[tid];
       const unsigned long long key = tid < kRcSlots ? rc_keys[tid] : kRcNoKey;
       int                      n   = 0;
       for (int u = 0; u < 8; u++)
@@ -1168,7 +1175,12 @@ __global__ __launch_bounds__(256) void k_spmv_rowclass(int nrows, const unsigned
          n_cls = (int)rclass[r];
          if (MODE == MODE_PLAIN) { if (beta != 0.0) n_e0 = yin[r]; if (DOT) n_e1 = w[r]; }
          else if (MODE == MODE_RESID) n_e0 = b[r];
-         else { n_e0 = b[r]; n_e1 = dinv[r]; n_e2 = x[r]; }
+         else
+         {
+            n_e0 = b[r];
+            n_e2 = x[r];
+            if (!CD || n_cls >= 128) n_e1 = dinv[r];
+         }
       }
    };
    // (runs of 2-16 consecutive tiles per workgroup, for L1 reuse of the neighbouring x lines, measured no faster)
@@ -1178,7 +1190,7 @@ __global__ __launch_bounds__(256) void k_spmv_rowclass(int nrows, const unsigned
       const int    r    = xcd * per + tile * 256 + tid;
       const bool   live = r < nrows;
       const int    cls  = n_cls;
-      const double e0 = n_e0, e1 = n_e1, e2 = n_e2;
+      const double e0 = n_e0, e1 = (CD && cls < 128) ? sdv[cls] : n_e1, e2 = n_e2;
       double       sum = 0.0;
       fetch(tile + nslot);
       if (cls < 128)
@@ -2216,6 +2228,8 @@ static SpmvForm spmv_form(const DCsr &A, bool split)
 //   fold: the Jacobi sweep after a prolongation in its folded storage form (jacobi_folded).  Taken by a whole MODE_JACOBI launch without
 //     a dot, which then streams *fold = P~ = P - D^-1 (A P) instead of A -- x is the coarse correction and yin the row's own iterate.
 //     The launch stays a MODE_JACOBI launch on A: a probe armed on (A, Jacobi) brackets it like any other sweep of that operator.
+//   cdinv: the divisors of dinv by row class (class_divisors).  Taken by a MODE_JACOBI launch on a row-class coded operator; null, or
+//     any other storage form: dinv[r], as ever.
 struct SpmvCall {
    SpmvCall(const double *x_, double *out_) : x(const_cast<double *>(x_)), out(out_) {}
    double       *x; // with a halo plan the ghost tail of x is refreshed (callers pass writable vectors there)
@@ -2226,6 +2240,7 @@ struct SpmvCall {
    const double *dinv2   = nullptr;
    double       *out2    = nullptr;
    const DCsr   *fold    = nullptr;
+   const double *cdinv   = nullptr;
 };
 
 // The template arguments a product kernel exists for, beside MODE and DOT: every rule, once.  k_spmv_win has all six; k_spmv_stream
@@ -2292,18 +2307,21 @@ static bool launch_spmv_impl(const DCsr &A_in, const SpmvCall &c, int nown = -1)
    {
       const int per  = (((A.nrows + 7) >> 3) + 255) / 256 * 256; // rows per XCD (as in the kernel)
       const int grid = DOT ? gmax : std::min(gmax, 8 * (per / 256));
+      const bool cd = MODE == MODE_JACOBI && form == SpmvForm::RowClass && c.cdinv;
       instantiate(
-         [&](auto SPLIT) {
-            if (form == SpmvForm::RowClass)
-               k_spmv_rowclass<MODE, DOT, SPLIT><<<grid, 256, 0, STREAM>>>(A.nrows, A.rclass.data(), A.rc_keys.data(), A.dict_val.data(),
-                                                                           A.dict_delta.data(), A.rowptr.data(), A.col.data(), A.val.data(), c.x,
-                                                                           c.alpha, c.beta, c.yin, c.b, c.dinv, c.w, c.out, c.partial, nown);
+         [&](auto SPLIT, auto CD) {
+            if constexpr (CD && MODE != MODE_JACOBI) spmv_no_kernel();
+            else if (form == SpmvForm::RowClass)
+               k_spmv_rowclass<MODE, DOT, SPLIT, CD><<<grid, 256, 0, STREAM>>>(A.nrows, A.rclass.data(), A.rc_keys.data(), A.dict_val.data(),
+                                                                               A.dict_delta.data(), A.rowptr.data(), A.col.data(), A.val.data(), c.x,
+                                                                               c.alpha, c.beta, c.yin, c.b, c.dinv, c.w, c.out, c.partial, nown,
+                                                                               CD ? c.cdinv : nullptr);
             else
                k_spmv_coded_row<MODE, DOT, SPLIT><<<grid, 256, 0, STREAM>>>(A.nrows, A.rowptr.data(), A.code.data(), A.dict_val.data(),
                                                                             A.dict_delta.data(), A.col.data(), A.val.data(), c.x, c.alpha, c.beta,
                                                                             c.yin, c.b, c.dinv, c.w, c.out, c.partial, SPLIT ? nown : 0);
          },
-         Flag{split});
+         Flag{split}, Flag{cd});
    }
    else if (form == SpmvForm::Window || form == SpmvForm::WindowRuns)
    {
@@ -2537,17 +2555,50 @@ void residual(const DCsr &A, const double *x, const double *b, double *out, cons
    c.b = b;
    launch_spmv<MODE_RESID, false>(A, halo, c);
 }
-void jacobi(const DCsr &A, const double *dinv, const double *b, const double *x_in, double *x_out, int dot_slot, const HaloPlan *halo)
+void jacobi(const DCsr &A, const double *dinv, const double *b, const double *x_in, double *x_out, int dot_slot, const HaloPlan *halo,
+            const double *cdinv)
 {
    SpmvCall c(x_in, x_out);
-   c.b    = b;
-   c.dinv = dinv;
+   c.b     = b;
+   c.dinv  = dinv;
+   c.cdinv = cdinv;
    if (dot_slot >= 0)
    {
       c.partial = Context::get().slot(dot_slot);
       launch_spmv<MODE_JACOBI, true>(A, halo, c);
    }
    else launch_spmv<MODE_JACOBI, false>(A, halo, c);
+}
+
+__global__ __launch_bounds__(256) void k_cdinv_collect(int n, const unsigned char *__restrict__ rclass, const double *__restrict__ dinv,
+                                                       double *table)
+{ // (rows of one class all store the same number when the table is usable at all; k_cdinv_verify decides)
+   const int i = blockIdx.x * 256 + threadIdx.x;
+   if (i < n && rclass[i] < 128) table[rclass[i]] = dinv[i];
+}
+__global__ __launch_bounds__(256) void k_cdinv_verify(int n, const unsigned char *__restrict__ rclass, const double *__restrict__ dinv,
+                                                      const double *__restrict__ table, int *bad)
+{
+   const int i = blockIdx.x * 256 + threadIdx.x;
+   if (i < n && rclass[i] < 128 && __double_as_longlong(table[rclass[i]]) != __double_as_longlong(dinv[i])) *bad = 1;
+}
+const unsigned char *row_classes(const DCsr &A) { return A.rowcoded == 1 ? A.rclass.data() : nullptr; }
+bool class_divisors(const DCsr &A, const double *dinv, DArray<double> &table)
+{
+   table.release();
+   spmv_prepare(A);
+   if (A.rowcoded != 1 || A.nrows < 1 || !dinv) return false;
+   table.alloc(128);
+   table.zero();
+   DArray<int> bad(1);
+   bad.zero();
+   const int g = ceil_div(A.nrows, 256);
+   k_cdinv_collect<<<g, 256, 0, STREAM>>>(A.nrows, A.rclass.data(), dinv, table.data());
+   k_cdinv_verify<<<g, 256, 0, STREAM>>>(A.nrows, A.rclass.data(), dinv, table.data(), bad.data());
+   int nb = 0;
+   bad.download(&nb, 1);
+   if (nb) table.release();
+   return nb == 0;
 }
 
 bool spmv_foldable(const DCsr &Pt)
@@ -2687,12 +2738,22 @@ __device__ __forceinline__ double slot_sum_256(const double *__restrict__ p)
 // block computes the same sum, block 0 stores it for the host's breakdown test.
 // Z0: the preconditioner's cycle opens with the zero-guess Jacobi sweep z0 = dinv0 .* r (Amg::first_sweep_*): written here, on
 // the r this kernel has just produced, instead of by a pass of its own over r and dinv0 (z0 may alias s: same index, read first)
-template <bool FIN, bool Z0>
+// XUP = false: x += alpha p is left to k_cg_dir, which loads p[i] anyway (x and p are then not touched here: 3 V less)
+// Z0 = 2: the divisor of row i by its class, cdinv[rclass[i]] (class_divisors; the table sits in LDS), dinv0[i] for the CSR rows: a
+// class byte in place of a double per row
+template <bool FIN, int Z0, bool XUP>
 __global__ __launch_bounds__(256) void k_cg_update(int n, double *scalars, int gamma_idx, const double *__restrict__ p,
                                                    const double *s, double *__restrict__ x, double *__restrict__ r,
                                                    double *__restrict__ partial, const double *__restrict__ sp_partials,
-                                                   const double *__restrict__ dinv0, double *z0)
+                                                   const double *__restrict__ dinv0, double *z0, const unsigned char *__restrict__ rclass,
+                                                   const double *__restrict__ cdinv)
 {
+   __shared__ double sdv[Z0 == 2 ? 128 : 1];
+   if (Z0 == 2)
+   {
+      if (threadIdx.x < 128) sdv[threadIdx.x] = cdinv[threadIdx.x];
+      __syncthreads();
+   }
    double sp;
    if (FIN)
    {
@@ -2704,31 +2765,46 @@ __global__ __launch_bounds__(256) void k_cg_update(int n, double *scalars, int g
    double       acc   = 0.0;
    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
    {
-      x[i] += alpha * p[i];
+      if (XUP) x[i] += alpha * p[i];
       const double ri = r[i] - alpha * s[i];
       r[i]            = ri;
-      if (Z0) z0[i] = dinv0[i] * ri;
+      if (Z0 == 1) z0[i] = dinv0[i] * ri;
+      if (Z0 == 2)
+      {
+         const int c = rclass[i];
+         z0[i]       = (c < 128 ? sdv[c] : dinv0[i]) * ri;
+      }
       acc += ri * ri;
    }
    acc = block_sum(acc);
    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
+template <bool FIN, int Z0>
+static void launch_cg_update(int n, int gamma_idx, const double *p, const double *s, double *x, double *r, double *rr, const double *spp,
+                             const double *dinv0, double *z0, const unsigned char *rclass, const double *cdinv)
+{
+   Context &c = Context::get();
+   if (x) k_cg_update<FIN, Z0, true><<<kRedBlocks, 256, 0, c.stream>>>(n, c.scalars, gamma_idx, p, s, x, r, rr, spp, dinv0, z0, rclass, cdinv);
+   else k_cg_update<FIN, Z0, false><<<kRedBlocks, 256, 0, c.stream>>>(n, c.scalars, gamma_idx, p, s, x, r, rr, spp, dinv0, z0, rclass, cdinv);
+}
 void cg_update(int n, int gamma_idx, const double *p, const double *s, double *x, double *r, int rr_slot, int sp_slot, const double *dinv0,
-               double *z0)
+               double *z0, const unsigned char *rclass, const double *cdinv)
 {
    Context &c = Context::get();
    const double *spp = sp_slot >= 0 ? c.slot(sp_slot) : nullptr;
-   if (spp && z0) k_cg_update<true, true><<<kRedBlocks, 256, 0, c.stream>>>(n, c.scalars, gamma_idx, p, s, x, r, c.slot(rr_slot), spp, dinv0, z0);
-   else if (spp) k_cg_update<true, false><<<kRedBlocks, 256, 0, c.stream>>>(n, c.scalars, gamma_idx, p, s, x, r, c.slot(rr_slot), spp, dinv0, z0);
-   else if (z0) k_cg_update<false, true><<<kRedBlocks, 256, 0, c.stream>>>(n, c.scalars, gamma_idx, p, s, x, r, c.slot(rr_slot), spp, dinv0, z0);
-   else k_cg_update<false, false><<<kRedBlocks, 256, 0, c.stream>>>(n, c.scalars, gamma_idx, p, s, x, r, c.slot(rr_slot), spp, dinv0, z0);
+   double       *rr  = c.slot(rr_slot);
+   const int     zm  = !z0 ? 0 : (rclass && cdinv) ? 2 : 1;
+   instantiate([&](auto FIN, auto Z0) { launch_cg_update<FIN, Z0>(n, gamma_idx, p, s, x, r, rr, spp, dinv0, z0, rclass, cdinv); },
+               Flag{spp != nullptr}, OneOf<0, 1, 2>{zm});
 }
 
 // FIN: one rank -- gamma_new = <r,z> (and <r,r> beside it) are finished here from block partials slots first_slot, first_slot + 1
 // into scalars gn, gn + 1, instead of by a finalize launch
-template <bool FIN>
+// XUP: the solution update of the iteration that ends here rides on this pass over p: x += alpha p with the update kernel's
+// alpha = scalars[go] / scalars[S_SP] (neither scalar is written between the two kernels), then p = z + beta p from the same load
+template <bool FIN, bool XUP>
 __global__ __launch_bounds__(256) void k_cg_dir(int n, double *scalars, int go, int gn, const double *__restrict__ z, double *__restrict__ p,
-                                                const double *__restrict__ partials2)
+                                                const double *__restrict__ partials2, double *__restrict__ x)
 {
    double g;
    if (FIN)
@@ -2741,14 +2817,40 @@ __global__ __launch_bounds__(256) void k_cg_dir(int n, double *scalars, int go, 
       }
    }
    else g = scalars[gn];
-   const double beta = g / scalars[go];
-   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) p[i] = z[i] + beta * p[i];
+   const double beta  = g / scalars[go];
+   const double alpha = XUP ? scalars[go] / scalars[S_SP] : 0.0;
+   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
+   {
+      const double pi = p[i];
+      if (XUP) x[i] += alpha * pi;
+      p[i] = z[i] + beta * pi;
+   }
 }
-void cg_direction(int n, int gamma_old_idx, int gamma_new_idx, const double *z, double *p, int first_slot)
+void cg_direction(int n, int gamma_old_idx, int gamma_new_idx, const double *z, double *p, int first_slot, double *x)
 {
    Context &c = Context::get();
-   if (first_slot >= 0) k_cg_dir<true><<<std::max(ew_grid(n), 1), 256, 0, STREAM>>>(n, c.scalars, gamma_old_idx, gamma_new_idx, z, p, c.slot(first_slot));
-   else if (n) k_cg_dir<false><<<ew_grid(n), 256, 0, STREAM>>>(n, c.scalars, gamma_old_idx, gamma_new_idx, z, p, nullptr);
+   if (first_slot >= 0)
+   {
+      const int g = std::max(ew_grid(n), 1);
+      if (x) k_cg_dir<true, true><<<g, 256, 0, STREAM>>>(n, c.scalars, gamma_old_idx, gamma_new_idx, z, p, c.slot(first_slot), x);
+      else k_cg_dir<true, false><<<g, 256, 0, STREAM>>>(n, c.scalars, gamma_old_idx, gamma_new_idx, z, p, c.slot(first_slot), nullptr);
+   }
+   else if (n)
+   {
+      if (x) k_cg_dir<false, true><<<ew_grid(n), 256, 0, STREAM>>>(n, c.scalars, gamma_old_idx, gamma_new_idx, z, p, nullptr, x);
+      else k_cg_dir<false, false><<<ew_grid(n), 256, 0, STREAM>>>(n, c.scalars, gamma_old_idx, gamma_new_idx, z, p, nullptr, nullptr);
+   }
+}
+
+__global__ __launch_bounds__(256) void k_cg_flush_x(int n, const double *__restrict__ scalars, int gamma_idx, const double *__restrict__ p,
+                                                    double *__restrict__ x)
+{
+   const double alpha = scalars[gamma_idx] / scalars[S_SP];
+   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) x[i] += alpha * p[i];
+}
+void cg_flush_x(int n, int gamma_idx, const double *p, double *x)
+{
+   if (n) k_cg_flush_x<<<ew_grid(n), 256, 0, STREAM>>>(n, Context::get().scalars, gamma_idx, p, x);
 }
 
 // One step of the single-reduction (Chronopoulos-Gear) form of PCG, all vector work of an iteration in one pass:

@@ -5,6 +5,7 @@
 #include "hda_amg.h"
 
 #include <functional>
+#include <limits>
 
 namespace hda {
 
@@ -48,8 +49,17 @@ struct LinOp {
    LinOp(const DCsr &a, const HaloPlan *h, size_t len) : A(&a), halo(h), veclen(std::max(len, (size_t)std::max(a.ncols, a.nrows))) {}
 };
 
+// What the caller of pcg() already knows about its operands (the vector objects of hda_hypre.h keep track); nothing by default.
+//   x_zero: x is exactly +0.0 everywhere, so r = b - A x is b bit for bit (every row sum of A x is +0.0) and PCG copies b
+//           instead of staging x and running a residual pass
+//   bb:     <b,b> as dot() + finalize() give it (a NaN: not known), in place of the same reduction and its read-back
+struct PcgKnown {
+   bool   x_zero = false;
+   double bb     = std::numeric_limits<double>::quiet_NaN();
+};
+
 // hypre_PCGSolve (reached from solver_ops[SOLVER_PCG].solve, src/internal/solver.c:211)
-KrylovResult pcg(const LinOp &op, const PrecondFn &M, const KrylovParams &p, const double *b, double *x);
+KrylovResult pcg(const LinOp &op, const PrecondFn &M, const KrylovParams &p, const double *b, double *x, const PcgKnown *known = nullptr);
 // hypre_GMRESSolve (solver_ops[SOLVER_GMRES], src/internal/solver.c:217-228)
 KrylovResult gmres(const LinOp &op, const PrecondFn &M, const KrylovParams &p, const double *b, double *x);
 // hypre_FlexGMRESSolve (solver_ops[SOLVER_FGMRES], solver.c:229-240) and hypre_BiCGSTABSolve (solver.c:241-252)

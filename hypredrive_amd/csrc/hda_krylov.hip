@@ -46,7 +46,11 @@ double pcg_iteration_bytes(const DCsr &A, bool format)
 {
    const double n = A.nrows;
    // SpMV + fused <s,p> (reads p again: 8n) ; x,r update + <r,r> : 48n ; p = z + beta p : 24n
-   return (matrix_stream_bytes(A, format) + rowptr_stream_bytes(A, format) + 8.0 * A.ncols + 8.0 * n) + 8.0 * n + 48.0 * n + 24.0 * n;
+   // format: as the kernels run -- with x += alpha p on the direction kernel (HDA_DEFER_X) the update moves r, s: 24n, the direction
+   // z, p, x: 40n
+   const char  *dxe = getenv("HDA_DEFER_X");
+   const double vec = (format && !(dxe && atoi(dxe) == 0)) ? 24.0 * n + 40.0 * n : 48.0 * n + 24.0 * n;
+   return (matrix_stream_bytes(A, format) + rowptr_stream_bytes(A, format) + 8.0 * A.ncols + 8.0 * n) + 8.0 * n + vec;
 }
 
 // Single-reduction PCG (Chronopoulos & Gear 1989), opt-in: HDA_PCG_SINGLE_REDUCE=1.  hypre's recurrence needs three global sums per
@@ -146,7 +150,7 @@ static KrylovResult pcg_single_reduction(const LinOp &op, const PrecondFn &M, co
    return res;
 }
 
-KrylovResult pcg(const LinOp &op, const PrecondFn &M, const KrylovParams &kp, const double *b, double *x)
+KrylovResult pcg(const LinOp &op, const PrecondFn &M, const KrylovParams &kp, const double *b, double *x, const PcgKnown *known)
 {
    NestedScope  scope;
    if (kp.two_norm && !scope.nested)
@@ -172,7 +176,8 @@ KrylovResult pcg(const LinOp &op, const PrecondFn &M, const KrylovParams &kp, co
    struct FsReset { // also on the way out through an exception: a flag left set would make the next solver's first cycle skip its sweep
       ~FsReset() { first_sweep_fusion() = FirstSweepFusion(); }
    } fs_reset;
-   const double *z0_dinv = nullptr;
+   const double *z0_dinv = nullptr, *z0_cdinv = nullptr; // (cdinv, rclass: the same divisors by row class, where the offer has them)
+   const unsigned char *z0_rclass = nullptr;
    double       *z0_dest = nullptr;
    bool          z0_self = false; // the offered destination is the output vector of the next application
    auto precond = [&](const double *rr, double *zz, int slot) {
@@ -188,6 +193,8 @@ KrylovResult pcg(const LinOp &op, const PrecondFn &M, const KrylovParams &kp, co
       const bool mine = fs.valid && fs.n == n; // (an offer about an operator of another size is not for this loop)
       z0_dinv = mine ? fs.dinv : nullptr;
       z0_dest = mine ? fs.dest : nullptr;
+      z0_cdinv  = mine ? fs.cdinv : nullptr;
+      z0_rclass = mine ? fs.rclass : nullptr;
       z0_self = mine && fs.dest == nullptr;
       fs.valid = false;
    };
@@ -198,20 +205,25 @@ KrylovResult pcg(const LinOp &op, const PrecondFn &M, const KrylovParams &kp, co
    const char *ffe = getenv("HDA_FUSE_FINALIZE"); // (read per solve: the tests switch it inside one process)
    const int   fl  = (Comm::world().size == 1) ? (ffe ? atoi(ffe) : 1) : 0;
    const bool  fin = fl >= 1, fin2 = fl >= 2;
+   // HDA_DEFER_X (default on; 0 = the update kernel adds alpha p itself): x += alpha p rides on the direction kernel, which loads the
+   // same p a preconditioner application later -- one pass over x and one over p less per iteration.  alpha is the update kernel's
+   // quotient scalars[go] / scalars[S_SP]: neither scalar is written before the direction step (a nested solve inside the
+   // preconditioner puts the block back, NestedScope), so every term is added once, in the same order, with the same bits.  An
+   // exit between the update and its direction step adds the outstanding term with cg_flush_x.
+   const char *dxe     = getenv("HDA_DEFER_X"); // (read per solve)
+   const bool  defer_x = !(dxe && atoi(dxe) == 0);
+   double     *xd      = defer_x ? x : nullptr; // what the direction kernel gets
 
    // bi_prod = <b,b> (two_norm) or <C b, b>
    double bi_prod;
-   if (kp.two_norm)
-   {
-      dot(n, b, b, 0);
-      finalize(0, S_BB);
-   }
+   if (kp.two_norm && known && !std::isnan(known->bb)) bi_prod = known->bb;
    else
    {
-      precond(b, p.data(), 0);
+      if (kp.two_norm) dot(n, b, b, 0);
+      else precond(b, p.data(), 0);
       finalize(0, S_BB);
+      bi_prod = read_scalar(S_BB);
    }
-   bi_prod = read_scalar(S_BB);
    if (bi_prod == 0.0)
    {
       copy(n, b, x); // hypre: zero rhs => x = b = 0
@@ -225,8 +237,12 @@ KrylovResult pcg(const LinOp &op, const PrecondFn &M, const KrylovParams &kp, co
       if (a2 > eps) eps = a2;
    }
    // r = b - A x ; p = C r ; gamma = <r,p>   (x has no ghost tail: stage it through p)
-   copy(n, x, p.data());
-   residual(A, p.data(), b, r.data(), op.halo);
+   if (known && known->x_zero) copy(n, b, r.data()); // b - A 0: every row sum is +0.0, and b - (+0.0) is b, a -0.0 included
+   else
+   {
+      copy(n, x, p.data());
+      residual(A, p.data(), b, r.data(), op.halo);
+   }
    precond(r.data(), p.data(), 2);
    dot(n, r.data(), r.data(), 3);
    finalize_n(2, 2, S_GAMMA0); // <r,z> -> S_GAMMA0, <r,r> -> S_RR0: one kernel, one all-reduce of two doubles
@@ -234,7 +250,7 @@ KrylovResult pcg(const LinOp &op, const PrecondFn &M, const KrylovParams &kp, co
    wait_event(ctx.ev);
    double i_prod = kp.two_norm ? ctx.host_scalars[S_RR0] : ctx.host_scalars[S_GAMMA0];
    res.hist.push_back(std::sqrt(std::fabs(i_prod)));
-   int it = 0;
+   int it = 0, x_term = -1; // x_term: the gamma scalar of an update whose alpha p is not in x yet
    std::vector<hipEvent_t> evs;
    // HDA_FUSE_DOTS=0: every inner product gets its own all-reduce (the unfused path the fused one is tested against)
    static const bool fuse_dots = !(getenv("HDA_FUSE_DOTS") && atoi(getenv("HDA_FUSE_DOTS")) == 0);
@@ -257,7 +273,8 @@ KrylovResult pcg(const LinOp &op, const PrecondFn &M, const KrylovParams &kp, co
          spmv_dot(A, p.data(), s.data(), p.data(), 0, op.halo);
       if (!fin) finalize(0, S_SP);
       double *z0 = z0_dinv ? (z0_self ? s.data() : z0_dest) : nullptr;
-      cg_update(n, go, p.data(), s.data(), x, r.data(), 3, fin ? 0 : -1, z0_dinv, z0);
+      cg_update(n, go, p.data(), s.data(), defer_x ? nullptr : x, r.data(), 3, fin ? 0 : -1, z0_dinv, z0, z0_rclass, z0_cdinv);
+      x_term = defer_x ? go : -1;
       // The stopping test of the two-norm variant needs only <r,r>.  hypre applies the preconditioner
       // before testing, so its last V-cycle is computed and thrown away; here, once the history says the
       // tolerance is within reach, the host waits for <r,r> BEFORE enqueueing that V-cycle and skips it
@@ -304,12 +321,13 @@ KrylovResult pcg(const LinOp &op, const PrecondFn &M, const KrylovParams &kp, co
          fs.in   = r.data();
          fs.out  = s.data();
          precond(r.data(), s.data(), 2);
-         if (fin2) cg_direction(n, go, gn, s.data(), p.data(), 2); // (finishes slot 3 into rn once more: the same sum)
+         if (fin2) cg_direction(n, go, gn, s.data(), p.data(), 2, xd); // (finishes slot 3 into rn once more: the same sum)
          else
          {
             finalize(2, gn);
-            cg_direction(n, go, gn, s.data(), p.data());
+            cg_direction(n, go, gn, s.data(), p.data(), -1, xd);
          }
+         x_term = -1;
          continue;
       }
       if (!fuse_dots) finalize(3, rn);
@@ -319,7 +337,7 @@ KrylovResult pcg(const LinOp &op, const PrecondFn &M, const KrylovParams &kp, co
       precond(r.data(), s.data(), 2);
       if (fin2 && fuse_dots)
       {
-         cg_direction(n, go, gn, s.data(), p.data(), 2);
+         cg_direction(n, go, gn, s.data(), p.data(), 2, xd);
          read_scalars_async(S_GAMMA0, 5);
       }
       else
@@ -327,12 +345,14 @@ KrylovResult pcg(const LinOp &op, const PrecondFn &M, const KrylovParams &kp, co
          if (fuse_dots) finalize_n(2, 2, gn);
          else finalize(2, gn);
          read_scalars_async(S_GAMMA0, 5);
-         cg_direction(n, go, gn, s.data(), p.data());
+         cg_direction(n, go, gn, s.data(), p.data(), -1, xd);
       }
+      x_term = -1;
       test();
       if (stop) break;
    }
    fs = FirstSweepFusion();
+   if (x_term >= 0) cg_flush_x(n, x_term, p.data(), x); // left before the direction step: convergence or a breakdown seen on the near path
    ctx.sync();
    gs_free_check();
    for (size_t e = 0; e + 1 < evs.size(); e += 2)

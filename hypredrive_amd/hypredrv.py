@@ -80,6 +80,7 @@ def lib():
         "HYPREDRV_StatsLevelGetEntry": [vp, C.c_int, C.c_int, ip, ip, ip, dp, dp],
         "HYPREDRV_StatsLevelPrint": [vp, C.c_int],
         "HYPREDRV_AMD_SolvePhaseBytes": [vp, dp, dp],
+        "HYPREDRV_AMD_LastResidualNorms": [vp, dp, dp, ip],
         "HYPREDRV_AMD_ProbeDominant": [vp, C.c_int, ip, dp, dp, ip],
     }
     for name, args in sig.items():
@@ -268,6 +269,12 @@ class Hypredrv:
         it, vc = (C.c_double * 2)(), (C.c_double * 2)()
         check(lib().HYPREDRV_AMD_SolvePhaseBytes(self.h, it, vc))
         return (it[0], it[1]), (vc[0], vc[1])
+
+    def residual_norms(self):
+        """(r0, relative residual) of the last apply in full precision, and whether x is known to be the untouched zero fill now"""
+        r0, rel, z = C.c_double(), C.c_double(), C.c_int()
+        check(lib().HYPREDRV_AMD_LastResidualNorms(self.h, C.byref(r0), C.byref(rel), C.byref(z)))
+        return r0.value, rel.value, bool(z.value)
 
     def probe_dominant_arm(self):
         """Time every Jacobi-sweep launch on this rank's largest plain-CSR operator; returns (level, rows, cols, nnz)."""

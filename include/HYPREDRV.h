@@ -166,6 +166,9 @@ HYPREDRV_EXPORT_SYMBOL const char *HYPREDRV_AMD_LastErrorMessage(void);
 /* measurement hook of bench.py: bytes this rank streams per Krylov iteration and per V-cycle,
  * [0] as CSR, [1] in the formats actually read */
 HYPREDRV_EXPORT_SYMBOL uint32_t HYPREDRV_AMD_SolvePhaseBytes(HYPREDRV_t hypredrv, double iteration[2], double vcycle[2]);
+/* the last LinearSolverApply's ||b - A x0|| and ||b - A x|| / ||b|| as the statistics table holds them, in full precision; and
+ * whether the solution vector is, right now, known to be the library's untouched zero fill (0 / 1) */
+HYPREDRV_EXPORT_SYMBOL uint32_t HYPREDRV_AMD_LastResidualNorms(HYPREDRV_t hypredrv, double *r0, double *rel, int *x_known_zero);
 /* measurement hook of bench.py (N > 1): arm != 0 brackets every Jacobi-sweep launch on this rank's largest
  * plain-CSR operator with HIP events (returns its level and local rows/cols/nnz); arm == 0 returns the
  * average launch duration and disarms */

@@ -57,10 +57,12 @@ def compute(fdir, wdir, tag, summary_csv=None):
 
     n = 256 ** 3
     cal_f, cal_w = med("k_cg_dir", "F", True), med("k_cg_dir", "W", True)
-    fetch_factor = (2 * 8.0 * n / 1024) / cal_f if cal_f else 2.0
-    write_factor = (8.0 * n / 1024) / cal_w if cal_w else 1.0
+    # k_cg_dir<FIN, true>: the direction kernel that also carries x += alpha p reads z, p, x and writes p, x
+    cal_reads, cal_writes = (3, 2) if any("k_cg_dir<" in k and ", true>(" in k for k in byk) else (2, 1)
+    fetch_factor = (cal_reads * 8.0 * n / 1024) / cal_f if cal_f else 2.0
+    write_factor = (cal_writes * 8.0 * n / 1024) / cal_w if cal_w else 1.0
     out = {"formula": "traffic = fetch_factor * FETCH_SIZE*1024 + write_factor * WRITE_SIZE*1024",
-           "calibration": {"kernel": "k_cg_dir on 256^3 (reads z,p = 268435456 B, writes p = 134217728 B, 8 B/lane streaming)",
+           "calibration": {"kernel": f"k_cg_dir on 256^3 (reads {cal_reads} vectors, writes {cal_writes}, 134217728 B each, 8 B/lane streaming)",
                            "FETCH_SIZE_KB": cal_f, "WRITE_SIZE_KB": cal_w, "fetch_factor": fetch_factor, "write_factor": write_factor},
            "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --steps 1 --warmup 0 "
                      f"--no-cpu-baseline --no-kernel-table; summary in {os.path.basename(tag)}_pmc_summary.csv"}
