@@ -28,6 +28,8 @@ class AmgParams(C.Structure):
                 ("ilu_tri_solve", C.c_int), ("ilu_lower_it", C.c_int), ("ilu_upper_it", C.c_int),
                 ("restrict_type", C.c_int), ("restrict_strong_th", C.c_double), ("restrict_filter_th", C.c_double), ("relax_points", C.c_int),
                 ("agg_p12_pmax", C.c_int), ("agg_p12_trunc_factor", C.c_double),
+                ("smooth_type", C.c_int), ("fsai_num_levels", C.c_int), ("fsai_max_nnz_row", C.c_int), ("fsai_eig_max_iters", C.c_int),
+                ("fsai_threshold", C.c_double),
                 ("agg_num_levels", C.c_int), ("agg_num_paths", C.c_int), ("agg_interp_type", C.c_int),
                 ("agg_pmax", C.c_int), ("agg_trunc_factor", C.c_double),
                 ("blocks", C.c_int), ("block_part", C.POINTER(C.c_int64)), ("struct_size", C.c_int)]
@@ -96,6 +98,7 @@ SYMBOLS = [
     "hda_schwarz_create", "hda_schwarz_domains", "hda_schwarz_info", "hda_precond_time",
     "hda_spgemm_last_route", "hda_sort_rows_last_route",
     "hda_ams_default_amg_params", "hda_ams_create", "hda_ams_matrix", "hda_ams_info",
+    "hda_fsai_create", "hda_fsai_factor", "hda_fsai_info",
 ]
 
 
@@ -193,6 +196,9 @@ def load():
     L.hda_ilu_create_blocks.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int64), P(vp)]
     L.hda_ilu_blocks.argtypes = [vp, C.c_int]
     L.hda_schwarz_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int64), C.c_int, C.c_double, P(vp)]
+    L.hda_fsai_create.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int64), P(vp)]
+    L.hda_fsai_factor.argtypes = [vp, C.c_int, P(vp)]
+    L.hda_fsai_info.argtypes = [vp, C.c_int, P(C.c_int64), P(C.c_double)]
     L.hda_schwarz_domains.argtypes = [vp, P(C.c_int), ip, ip]
     L.hda_schwarz_info.argtypes = [vp, P(C.c_int64), P(C.c_double)]
     L.hda_precond_time.argtypes = [vp, C.c_int, P(C.c_double)]
@@ -608,6 +614,15 @@ class Amg:
         _check(load().hda_ilu_factors(self.h, level, C.byref(out)))
         return Csr(out, owned=False, keep=self)
 
+    def fsai_factor(self, level):
+        """G of the static FSAI smoother (amg.smoother.type fsai) of a level."""
+        out = C.c_void_p()
+        _check(load().hda_fsai_factor(self.h, level, C.byref(out)))
+        return Csr(out, owned=False, keep=self)
+
+    def fsai_info(self, level):
+        return _fsai_info(self.h, level)
+
     def level_cf(self, level):
         n = self.level_matrix(level, 0).nrows
         cf = np.zeros(n, dtype=np.int32)
@@ -829,6 +844,55 @@ class Schwarz:
         return z
 
 
+def _fsai_info(h, level):
+    v, d = (C.c_int64 * 9)(), (C.c_double * 6)()
+    _check(load().hda_fsai_info(h, level, v, d))
+    return dict(n=v[0], nnz_factor=v[1], fallback_rows=v[2], blocks=v[3], class_rows={4: v[4], 8: v[5], 16: v[6], 32: v[7], 64: v[8]},
+                omega=d[0], apply_bytes=d[1], setup_ms=dict(pattern=d[2], local=d[3], transpose=d[4], omega=d[5]))
+
+
+class Fsai:
+    """'preconditioner: fsai' with algo_type bj-sfsai: the static factorised sparse approximate inverse
+    M^-1 = omega G^T G; usable as amg= in pcg()/gmres()/fgmres()/bicgstab()."""
+
+    def __init__(self, A, num_levels=1, threshold=1e-3, max_nnz_row=15, eig_max_iters=5, max_iter=1, blocks=1, block_part=None):
+        """blocks: 1 one block, 0 the setup's choice, V the even split unless block_part names the V + 1 row starts"""
+        self.A = A
+        self.h = C.c_void_p()
+        bp = None
+        if block_part is not None:
+            bp = np.ascontiguousarray(block_part, dtype=np.int64)
+            blocks = len(bp) - 1
+        _check(load().hda_fsai_create(A.h, num_levels, threshold, max_nnz_row, eig_max_iters, max_iter, blocks,
+                                      None if bp is None else bp.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(self.h)))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            load().hda_amg_destroy(self.h)
+            self.h = None
+
+    def factor(self):
+        """G: rows column-sorted, the diagonal last"""
+        out = C.c_void_p()
+        _check(load().hda_fsai_factor(self.h, -1, C.byref(out)))
+        return Csr(out, owned=False, keep=self)
+
+    def info(self):
+        """dict: n, nnz_factor, fallback_rows, blocks, class_rows (rows per lane class), omega, apply_bytes, setup_ms"""
+        return _fsai_info(self.h, -1)
+
+    @property
+    def omega(self):
+        return self.info()["omega"]
+
+    def apply(self, r):
+        """One application from a zero guess (max_iter iterations x += omega G^T G (r - A x))."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        z = np.zeros_like(r)
+        _check(load().hda_amg_vcycle(self.h, _dp(r), _dp(z)))
+        return z
+
+
 class Ams:
     """'preconditioner: ams': the auxiliary-space Maxwell preconditioner for A (n_e x n_e) with the discrete gradient
     G (n_e x n_v, a Csr) and coords = the vertex coordinate vectors; usable as amg= in pcg()/gmres()/fgmres()/bicgstab().
@@ -896,7 +960,7 @@ class Ams:
 
 
 def precond_time(M, reps=20):
-    """Average device ms of one application of an Ilu / Schwarz / Ams handle (vectors stay on the device)."""
+    """Average device ms of one application of an Ilu / Schwarz / Ams / Fsai handle (vectors stay on the device)."""
     ms = C.c_double()
     _check(load().hda_precond_time(M.h, reps, C.byref(ms)))
     return ms.value

@@ -82,6 +82,12 @@ struct AmgParams {
    // more than two); points_down / points_up, when not empty, name every sweep of that direction (HYPRE_BoomerAMGSetGridRelaxPoints)
    int              relax_points = 0;
    std::vector<int> points_down, points_up;
+   // complex smoother type 4: static FSAI (hda_fsai.hip) in the place of the ILU of type 5; of `fsai` the pattern and scaling numbers
+   // are read (max_iter is the smoother's smooth_num_sweeps, the blocks are the hierarchy's)
+   struct FsaiNumbers {
+      int    num_levels = 1, max_nnz_row = 15, eig_max_iters = 5;
+      double threshold = 1e-3;
+   } fsai;
 };
 int amg_auto_blocks(const DCsr &A); // the setup's choice for blocks = 0
 
@@ -234,6 +240,41 @@ class Schwarz {
 };
 void schwarz_solve(Schwarz &S, const DCsr &A, const double *b, double *x, bool zero_guess, DArray<double> &r, DArray<double> &c);
 
+// static factorised sparse approximate inverse (hda_fsai.hip): the algo_type bj-sfsai of the reference's FSAI_args
+// (src/internal/fsai.c) as this project defines it -- G on the lower-triangular pattern of a thresholded power of the scaled |A|, one
+// small SPD solve per row, M^-1 = omega G^T G.  One rank.
+struct FsaiParams {
+   int                    num_levels = 1;    // power of the scaled operator the pattern is taken from
+   double                 threshold  = 1e-3; // off-diagonal entries of S and of every product below it are dropped
+   int                    max_nnz_row = 15;  // entries of a row of G, the diagonal included (at most 64)
+   int                    eig_max_iters = 5; // power steps for omega; 0: omega = 1
+   int                    max_iter = 1;      // iterations x += omega G^T G (b - A x) per solve
+   int                    blocks = 1;        // as IluParams::blocks: the pattern of a row does not leave the row's block
+   std::vector<long long> block_part;
+};
+std::string fsai_params_refusal(const FsaiParams &p); // why these numbers are refused, by key name; empty = accepted
+class Fsai {
+ public:
+   // part (optional): row starts of the blocks, in place of blocks / block_part (the row blocks of an AMG level)
+   void        setup(const DCsr &A, const FsaiParams &p, const std::vector<int> *part = nullptr);
+   void        apply(const double *r, double *z); // z = omega G^T (G r); r and z must not alias
+   const DCsr &factor() const { return G; }       // rows column-sorted, diagonal last
+   const DCsr &factor_t() const { return GT; }
+   double      apply_bytes() const;               // algorithmic HBM bytes of one application (CSR figure)
+   FsaiParams  prm;
+   int         n = 0, nblocks = 1, fallback_rows = 0;
+   int         class_rows[5] = {0, 0, 0, 0, 0}; // rows solved with 4, 8, 16, 32, 64 lanes
+   double      omega = 1.0;
+   double      setup_ms[4] = {0, 0, 0, 0}; // pattern, local systems, transpose and plans, omega (host wall time, device synced)
+
+ private:
+   DCsr           G, GT;
+   DArray<double> work;
+};
+// max_iter (or iters > 0) iterations x += M^-1 (b - A x)
+void fsai_solve(Fsai &F, const DCsr &A, const HaloPlan *halo, const double *b, double *x, bool zero_guess, DArray<double> &r, DArray<double> &c,
+                int iters = 0);
+
 // PCG <-> preconditioner: a V-cycle from a zero guess that opens with the Jacobi sweep z0 = dinv .* r on level 0 lets its caller do
 // that multiplication where r is produced (PCG's update kernel: one pass over r and one launch less per iteration).  Thread-local,
 // like the hints of the C callback seam (hda_hypre.h PrecondHints).  The callee publishes an offer after every application
@@ -266,6 +307,8 @@ struct AmgLevel {
    bool           pg_ready = false; // set by the setup on EVERY rank or on none (the exchange it saves is a collective)
    GsPlan         gs;
    std::unique_ptr<Ilu> ilu; // complex smoother of this level, if any
+   std::unique_ptr<Fsai> fsai; // ... or its static FSAI (smooth_type 4); work vectors ilu_r / ilu_c
+   bool complex_smoother() const { return ilu || fsai; }
    // Chebyshev smoother (relax type 16): D^-1/2 scaling, polynomial coefficients, work vectors
    DArray<double> cheb_ds, cheb_v, cheb_w;
    double         cheb_coef[5] = {0, 0, 0, 0, 0}, cheb_max_eig = 0.0, cheb_min_eig = 0.0;

@@ -3000,7 +3000,7 @@ const double *Amg::class_dinv(int l, const double *dinv)
 
 bool Amg::level0_sweep(int dir, const double *b, const double *x, double *out, int dot_slot)
 {
-   HDA_REQUIRE(num_levels() > 1 && is_jacobi_type(dir == 0 ? prm.relax_down : prm.relax_up) && !levels[0].ilu && !dist,
+   HDA_REQUIRE(num_levels() > 1 && is_jacobi_type(dir == 0 ? prm.relax_down : prm.relax_up) && !levels[0].complex_smoother() && !dist,
                "level0_sweep: level 0 of this hierarchy is not relaxed by a Jacobi sweep on one rank");
    const double *dinv = sweep_dinv(0, dir, 0), *cd = class_dinv(0, dinv);
    jacobi(level_A(0), dinv, b, x, out, dot_slot, nullptr, cd);
@@ -3058,8 +3058,21 @@ void Amg::build_smoother_data(int l)
    // levels (counted from the finest level of the whole hierarchy), never on the coarsest
    if (prm.smooth_num_levels > 0)
    {
-      HDA_REQUIRE(prm.smooth_type == 5, "complex smoother: only ILU (type 5, bj-iluk with fill 0) is implemented");
-      if (l + level0 < prm.smooth_num_levels && !last)
+      HDA_REQUIRE(prm.smooth_type == 5 || prm.smooth_type == 4,
+                  "complex smoother: only ILU (type 5, bj-iluk with fill 0) and static FSAI (type 4, bj-sfsai) are implemented");
+      if (prm.smooth_type == 4 && l + level0 < prm.smooth_num_levels && !last)
+      { // static FSAI on the hierarchy's row blocks, where the ILU of type 5 sits
+         HDA_REQUIRE(!dist, "complex smoother: FSAI on a row-partitioned hierarchy is not implemented (one rank only)");
+         lv.fsai = std::make_unique<Fsai>();
+         FsaiParams fp;
+         fp.num_levels = prm.fsai.num_levels; fp.threshold = prm.fsai.threshold; fp.max_nnz_row = prm.fsai.max_nnz_row;
+         fp.eig_max_iters = prm.fsai.eig_max_iters;
+         fp.max_iter      = std::max(prm.smooth_num_sweeps, 1);
+         lv.fsai->setup(Al, fp, nblk > 1 ? &lv.blk_part : nullptr);
+         lv.ilu_r.alloc((size_t)std::max(Al.nrows, 1));
+         lv.ilu_c.alloc((size_t)std::max(Al.nrows, 1));
+      }
+      else if (l + level0 < prm.smooth_num_levels && !last)
       {
          lv.ilu = std::make_unique<Ilu>();
          IluParams ip = prm.ilu;
@@ -3131,7 +3144,7 @@ bool Amg::fold_level(int l)
    if (lv.Pt.nrows == 0) return false; // no A P kept: level 0, the coarsest level, row partitions, a replicated tail
    if (dist || l < 1 || l >= num_levels() - 1) return refuse("level");
    if (!is_jacobi_type(prm.relax_up) || prm.sweeps_up < 1) return refuse("no Jacobi sweep opens the up leg");
-   if (lv.ilu) return refuse("complex smoother");
+   if (lv.complex_smoother()) return refuse("complex smoother");
    if (sweep_points(1, 0) != 0) return refuse("F / C relaxation");
    DCsr &M = lv.Pt;
    HDA_REQUIRE(M.nrows == Al.nrows && M.ncols == lv.P.ncols, "folded up leg: A P does not have the shape of P");
@@ -3655,6 +3668,13 @@ double Amg::vcycle_bytes(bool format) const
          s += prm.sweeps_down > 0 ? app + (prm.sweeps_down * it - 1) * step : 0.0;
          s += prm.sweeps_up * it * step;
       }
+      else if (levels[l].fsai)
+      {
+         const double app = levels[l].fsai->apply_bytes(), step = spmv_bytes(A, format) + 8.0 * n + app + 24.0 * n;
+         const int    it  = levels[l].fsai->prm.max_iter;
+         s += prm.sweeps_down > 0 ? app + (prm.sweeps_down * it - 1) * step : 0.0;
+         s += prm.sweeps_up * it * step;
+      }
       else
       {
          s += 24.0 * n;                                            // zero-guess sweep: dinv, f -> u
@@ -3917,6 +3937,13 @@ void Amg::relax(int l, int type, const double *dinv, const double *b, double *&c
       if (dot_slot >= 0) dot(A.nrows, b, cur, dot_slot);
       return;
    }
+   if (levels[(size_t)l].fsai)
+   { // the same with the static FSAI (one rank)
+      AmgLevel &lv = levels[(size_t)l];
+      fsai_solve(*lv.fsai, A, nullptr, b, cur, zero_guess, lv.ilu_r, lv.ilu_c);
+      if (dot_slot >= 0) dot(A.nrows, b, cur, dot_slot);
+      return;
+   }
    if (type == 16)
    {
       cheby_sweep(l, b, cur, zero_guess, fresh);
@@ -4015,13 +4042,13 @@ FirstSweepFusion &first_sweep_fusion()
 bool Amg::first_sweep_fusable() const
 {
    const char *e = getenv("HDA_FUSE_Z0"); // (read per call: the tests switch it inside one process)
-   return !(e && atoi(e) == 0) && num_levels() > 1 && prm.sweeps_down >= 1 && is_jacobi_type(prm.relax_down) && !levels[0].ilu;
+   return !(e && atoi(e) == 0) && num_levels() > 1 && prm.sweeps_down >= 1 && is_jacobi_type(prm.relax_down) && !levels[0].complex_smoother();
 }
 // (the buffer choice of cycle() for zero_guess = true)
 double *Amg::first_sweep_dest(double *x)
 {
    auto oop = [&](int t) { return is_jacobi_type(t) || (levels[0].gs.nblk > 0 && (t == 3 || t == 4 || t == 13 || t == 14)); }; // as in cycle()
-   const int swaps0 = levels[0].ilu ? 0 : (oop(prm.relax_down) ? (prm.sweeps_down - (prm.sweeps_down > 0 ? 1 : 0)) : 0) +
+   const int swaps0 = levels[0].complex_smoother() ? 0 : (oop(prm.relax_down) ? (prm.sweeps_down - (prm.sweeps_down > 0 ? 1 : 0)) : 0) +
                                              (oop(prm.relax_up) ? prm.sweeps_up : 0);
    return (swaps0 & 1) ? levels[0].u2.data() : x;
 }
@@ -4073,7 +4100,7 @@ void Amg::cycle(const double *b, double *x, bool zero_guess, int dot_slot, bool 
    // level-0 buffer choice so the last out-of-place sweep lands in x
    // (a one-directional hybrid Gauss-Seidel sweep over row blocks is out of place like a Jacobi sweep, and in place from a zero guess)
    auto oop = [&](int t) { return is_jacobi_type(t) || (levels[0].gs.nblk > 0 && (t == 3 || t == 4 || t == 13 || t == 14)); };
-   const int swaps0 = levels[0].ilu ? 0 : // the complex smoother works in place
+   const int swaps0 = levels[0].complex_smoother() ? 0 : // the complex smoother works in place
                       (oop(prm.relax_down) ? (prm.sweeps_down - (zero_guess && prm.sweeps_down > 0 ? 1 : 0)) : 0) +
                       (oop(prm.relax_up) ? prm.sweeps_up : 0); // out-of-place sweeps on level 0
    double   *cur, *alt;
@@ -4099,7 +4126,7 @@ void Amg::cycle(const double *b, double *x, bool zero_guess, int dot_slot, bool 
       // the next level starts from a zero guess: a Jacobi-type first sweep there is u = dinv .* f, one multiplication per row that
       // the restriction kernel can do on the value it has just computed (one launch and one pass over f and dinv less per level)
       first_sweep_done = false;
-      if (fuse_first && l + 1 < L - 1 && prm.sweeps_down > 0 && is_jacobi_type(prm.relax_down) && !nx.ilu)
+      if (fuse_first && l + 1 < L - 1 && prm.sweeps_down > 0 && is_jacobi_type(prm.relax_down) && !nx.complex_smoother())
          first_sweep_done = spmv_with_scaled_copy(lv.R, lv.t.data(), nx.f.data(), sweep_dinv(l + 1, 0, 0), nx.u.data(), &lv.hR);
       else
          spmv(lv.R, 1.0, lv.t.data(), 0.0, nullptr, nx.f.data(), &lv.hR);

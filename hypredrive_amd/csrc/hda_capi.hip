@@ -27,6 +27,7 @@ struct hda_amg_s {
    std::unique_ptr<Mgr>                    mgr; // handle made by hda_mgr_create: the preconditioner is one MGR solve
    std::unique_ptr<Schwarz>                schwarz; // handle made by hda_schwarz_create: one Schwarz solve (work vectors: ilu_r / ilu_c)
    std::unique_ptr<Ams>                    ams; // handle made by hda_ams_create: one AMS application
+   std::unique_ptr<Fsai>                   fsai; // handle made by hda_fsai_create: one FSAI solve (work vectors: ilu_r / ilu_c)
    DArray<double>                          ilu_r, ilu_c;
    hda_csr_t                               A = nullptr;
    std::vector<std::unique_ptr<hda_csr_s>> views;
@@ -121,6 +122,8 @@ static void from_params(const AmgParams &d, hda_amg_params *p)
    p->agg_num_levels = d.agg_num_levels; p->agg_num_paths = d.agg_num_paths; p->agg_interp_type = d.agg_interp_type;
    p->agg_pmax = d.agg_pmax; p->agg_trunc_factor = d.agg_trunc_factor;
    p->agg_p12_pmax = d.agg_p12_pmax; p->agg_p12_trunc_factor = d.agg_p12_trunc_factor;
+   p->smooth_type = d.smooth_type; p->fsai_num_levels = d.fsai.num_levels; p->fsai_max_nnz_row = d.fsai.max_nnz_row;
+   p->fsai_eig_max_iters = d.fsai.eig_max_iters; p->fsai_threshold = d.fsai.threshold;
    p->blocks = d.blocks; p->block_part = nullptr;
    p->struct_size = (int)sizeof(hda_amg_params);
 }
@@ -153,6 +156,8 @@ static AmgParams to_params(const hda_amg_params *p)
    a.agg_num_levels = p->agg_num_levels; a.agg_num_paths = p->agg_num_paths; a.agg_interp_type = p->agg_interp_type;
    a.agg_pmax = p->agg_pmax; a.agg_trunc_factor = p->agg_trunc_factor;
    a.agg_p12_pmax = p->agg_p12_pmax; a.agg_p12_trunc_factor = p->agg_p12_trunc_factor;
+   a.smooth_type = p->smooth_type; a.fsai.num_levels = p->fsai_num_levels; a.fsai.max_nnz_row = p->fsai_max_nnz_row;
+   a.fsai.eig_max_iters = p->fsai_eig_max_iters; a.fsai.threshold = p->fsai_threshold;
    a.blocks = p->blocks;
    if (p->block_part && p->blocks > 1) a.block_part.assign(p->block_part, p->block_part + p->blocks + 1);
    return a;
@@ -850,6 +855,57 @@ extern "C" int hda_schwarz_info(hda_amg_t h, int64_t info[6], double setup_ms[4]
       for (int q = 0; q < 4; q++) setup_ms[q] = S.setup_ms[q];
    HDA_CATCH
 }
+// "preconditioner: fsai" (reference src/internal/fsai.c, algo_type bj-sfsai): the static FSAI of hda_fsai.hip
+extern "C" int hda_fsai_create(hda_csr_t A, int num_levels, double threshold, int max_nnz_row, int eig_max_iters, int max_iter, int blocks,
+                               const int64_t *block_part, hda_amg_t *out)
+{
+   HDA_TRY
+   HDA_REQUIRE(A && out, "hda_fsai_create: null argument");
+   auto h  = std::make_unique<hda_amg_s>();
+   h->A    = A;
+   h->fsai = std::make_unique<Fsai>();
+   FsaiParams p;
+   p.num_levels = num_levels; p.threshold = threshold; p.max_nnz_row = max_nnz_row; p.eig_max_iters = eig_max_iters; p.max_iter = max_iter;
+   p.blocks = blocks;
+   if (block_part && blocks > 1) p.block_part.assign(block_part, block_part + blocks + 1);
+   h->fsai->setup(A->get(), p);
+   *out = h.release();
+   HDA_CATCH
+}
+static Fsai *fsai_of(hda_amg_t h, int level)
+{
+   HDA_REQUIRE(h, "null handle");
+   if (level < 0) return h->fsai.get();
+   HDA_REQUIRE(h->amg && level < h->amg->num_levels(), "level out of range");
+   return h->amg->level(level).fsai.get();
+}
+extern "C" int hda_fsai_factor(hda_amg_t h, int level, hda_csr_t *out)
+{
+   HDA_TRY
+   const Fsai *F = fsai_of(h, level);
+   HDA_REQUIRE(F && out, "no FSAI factor on this handle / level");
+   auto v      = std::make_unique<hda_csr_s>();
+   v->borrowed = true;
+   v->ref      = &F->factor();
+   *out        = v.get();
+   h->views.push_back(std::move(v));
+   HDA_CATCH
+}
+extern "C" int hda_fsai_info(hda_amg_t h, int level, int64_t info[9], double vals[6])
+{
+   HDA_TRY
+   const Fsai *F = fsai_of(h, level);
+   HDA_REQUIRE(F && info, "no FSAI factor on this handle / level");
+   info[0] = F->n; info[1] = F->factor().nnz; info[2] = F->fallback_rows; info[3] = F->nblocks;
+   for (int q = 0; q < 5; q++) info[4 + q] = F->class_rows[q];
+   if (vals)
+   {
+      vals[0] = F->omega;
+      vals[1] = F->apply_bytes();
+      for (int q = 0; q < 4; q++) vals[2 + q] = F->setup_ms[q];
+   }
+   HDA_CATCH
+}
 // "preconditioner: ams" (reference src/internal/ams.c): auxiliary-space Maxwell preconditioner (hda_ams.hip)
 extern "C" void hda_ams_default_amg_params(hda_amg_params *p, int num_functions)
 {
@@ -915,7 +971,8 @@ extern "C" int hda_ams_info(hda_amg_t h, int64_t info[8], double ms[5])
 extern "C" int hda_precond_time(hda_amg_t h, int reps, double *avg_ms)
 {
    HDA_TRY
-   HDA_REQUIRE(h && (h->ilu || h->schwarz || h->ams) && avg_ms && reps > 0, "hda_precond_time: an ILU, Schwarz or AMS handle and reps > 0 are needed");
+   HDA_REQUIRE(h && (h->ilu || h->schwarz || h->ams || h->fsai) && avg_ms && reps > 0,
+               "hda_precond_time: an ILU, Schwarz, AMS or FSAI handle and reps > 0 are needed");
    Context       &ctx = Context::get();
    const DCsr    &m   = h->A->get();
    const size_t   nv  = (size_t)std::max(std::max(m.ncols, m.nrows), 1);
@@ -923,6 +980,7 @@ extern "C" int hda_precond_time(hda_amg_t h, int reps, double *avg_ms)
    fill((int)nv, 0.5, b.data());
    auto launch = [&]() {
       if (h->ams) h->ams->apply(b.data(), x.data());
+      else if (h->fsai) fsai_solve(*h->fsai, m, nullptr, b.data(), x.data(), true, h->ilu_r, h->ilu_c);
       else if (h->schwarz) schwarz_solve(*h->schwarz, m, b.data(), x.data(), true, h->ilu_r, h->ilu_c);
       else ilu_solve(*h->ilu, m, nullptr, b.data(), x.data(), true, h->ilu_r, h->ilu_c);
    };
@@ -1176,6 +1234,15 @@ extern "C" int hda_amg_vcycle(hda_amg_t h, const double *b, double *x)
       gs_free_check();
       return HDA_OK;
    }
+   if (h->fsai)
+   { // one application of the FSAI preconditioner from a zero guess
+      const DCsr    &m = h->A->get();
+      DArray<double> db, dx((size_t)std::max(std::max(m.ncols, m.nrows), 1));
+      db.upload(b, (size_t)m.nrows);
+      fsai_solve(*h->fsai, m, nullptr, db.data(), dx.data(), true, h->ilu_r, h->ilu_c);
+      dx.download(x, (size_t)m.nrows);
+      return HDA_OK;
+   }
    if (h->schwarz)
    { // one application of the Schwarz preconditioner from a zero guess
       const DCsr    &m = h->A->get();
@@ -1227,6 +1294,11 @@ static int run_krylov(int kind, hda_csr_t A, hda_amg_t amg, const hda_krylov_par
    else if (amg && amg->ams)
       M = [amg, &m](const double *r, double *z, int slot) {
          amg->ams->apply(r, z);
+         if (slot >= 0) dot(m.nrows, r, z, slot);
+      };
+   else if (amg && amg->fsai)
+      M = [amg, &m](const double *r, double *z, int slot) {
+         fsai_solve(*amg->fsai, m, nullptr, r, z, true, amg->ilu_r, amg->ilu_c);
          if (slot >= 0) dot(m.nrows, r, z, slot);
       };
    else if (amg && amg->schwarz)

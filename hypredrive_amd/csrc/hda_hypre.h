@@ -65,7 +65,7 @@ struct hypre_IJMatrix_struct {
    bool assemble_csr(const long long *indptr, const long long *cols, const double *data);
 };
 
-enum hda_solver_kind { HDA_SOLVER_PCG = 1, HDA_SOLVER_GMRES = 2, HDA_SOLVER_AMG = 3, HDA_SOLVER_ILU = 4, HDA_SOLVER_FGMRES = 5, HDA_SOLVER_BICGSTAB = 6, HDA_SOLVER_MGR = 7, HDA_SOLVER_SCHWARZ = 8, HDA_SOLVER_AMS = 9 };
+enum hda_solver_kind { HDA_SOLVER_PCG = 1, HDA_SOLVER_GMRES = 2, HDA_SOLVER_AMG = 3, HDA_SOLVER_ILU = 4, HDA_SOLVER_FGMRES = 5, HDA_SOLVER_BICGSTAB = 6, HDA_SOLVER_MGR = 7, HDA_SOLVER_SCHWARZ = 8, HDA_SOLVER_AMS = 9, HDA_SOLVER_FSAI = 10 };
 
 namespace hda {
 // addresses of the live solver objects THIS library created: an opaque HYPRE_Solver a caller installs with
@@ -104,6 +104,12 @@ struct hypre_Solver_struct {
    int                           sw_variant = 0, sw_overlap = 1, sw_domain_type = 2, sw_num_functions = 1, sw_nonsymm = 0, sw_local_solver = 0,
                                  sw_fill = 0, sw_max_iter = 1, sw_print_level = 0, sw_logging = 0;
    double                        sw_weight = 1.0, sw_tol = 0.0;
+   // HYPRE_FSAI* handle, and the FSAI arguments of BoomerAMG's complex smoother (HYPRE_BoomerAMGSetFSAI*): what the setters recorded
+   // (defaults: the reference's, src/internal/fsai.c:15-27 -- algo_type 1, the adaptive bj-afsai), checked at Setup
+   std::unique_ptr<hda::Fsai>    fsai;
+   hda::FsaiParams               fsaip;
+   int                           fs_algo = 1, fs_ls_type = 1, fs_max_steps = 5, fs_max_step_size = 3, fs_print_level = 0;
+   double                        fs_kap_tol = 1.0e-3, fs_tol = 0.0;
    // HYPRE_AMS* handle: what the setters recorded (defaults: the reference's GPU build, src/internal/ams.c:15-22), checked at Setup; G and
    // the coordinate vectors are borrowed, as in hypre
    std::unique_ptr<hda::Ams>     ams;
@@ -134,6 +140,9 @@ bool hypredrv_peek(void *hypredrv, const DCsr **A, const HaloPlan **halo, const 
 // Schwarz selections (hypre's numbers, reference src/internal/schwarz.c:48-66): the reason why this one is not built, empty = built
 std::string schwarz_refusal(int variant, int local_solver, int overlap, int fill, int max_iter, double tol, int num_functions,
                             int domain_type, int nonsymm);
+// FSAI selections (reference src/internal/fsai.c:45: algo_type 1 bj-afsai, 2 bj-afsai-omp, 3 bj-sfsai): the reason why this one is not
+// built, by the name of its key; empty = built
+std::string fsai_refusal(int algo_type, const FsaiParams &p, double tol);
 // error text of the last failed HYPRE_* call (HYPRE_GetError returns the code)
 const std::string &hypre_last_error();
 int                hypre_set_error(int code, const std::string &msg);

@@ -1346,10 +1346,24 @@ extern "C" HYPRE_Int HYPRE_BoomerAMGSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, 
    }
    if (s->smooth_num_levels > 0)
    {
-      HDA_REQUIRE(s->smooth_type == 5, "complex smoother: only ILU (smoother.type ilu) is implemented on MI355X; FSAI, Schwarz, Pilut, ParaSails, Euclid are not");
-      HDA_REQUIRE(s->ilu_type == 0 && s->ilu_fill == 0 && s->ilu_reordering == 0,
-                  "ILU smoother: only type bj-iluk with fill_level 0 and reordering 0 is implemented");
+      const std::string built = "complex smoother: ILU (smoother.type: ilu) and static FSAI (smoother.type: fsai with fsai.algo_type: bj-sfsai) are "
+                                "implemented on MI355X; ";
+      if (s->smooth_type != 5 && s->smooth_type != 4) throw Error(built + "Schwarz, Pilut, ParaSails and Euclid are not");
+      if (s->smooth_type == 4)
+      { // (max_iter, tolerance and print_level of the smoother's fsai block are not forwarded by amg.c:924-932: one step is num_sweeps iterations)
+         FsaiParams fp = s->fsaip;
+         fp.max_iter   = 1;
+         const std::string why = fsai_refusal(s->fs_algo, fp, 0.0);
+         if (!why.empty()) throw Error(built + why);
+         HDA_REQUIRE(Comm::world().size == 1, "complex smoother: FSAI in a world of more than one rank is not implemented (the pattern of a row partition "
+                                              "needs off-rank rows of the power of A); one rank with HDA_BLOCKS row blocks is");
+      }
+      else
+         HDA_REQUIRE(s->ilu_type == 0 && s->ilu_fill == 0 && s->ilu_reordering == 0,
+                     "ILU smoother: only type bj-iluk with fill_level 0 and reordering 0 is implemented");
    }
+   s->ap.fsai.num_levels = s->fsaip.num_levels; s->ap.fsai.max_nnz_row = s->fsaip.max_nnz_row; s->ap.fsai.eig_max_iters = s->fsaip.eig_max_iters;
+   s->ap.fsai.threshold  = s->fsaip.threshold;
    s->ap.smooth_type       = s->smooth_type;
    s->ap.smooth_num_levels = std::max(s->smooth_num_levels, 0);
    s->ap.ilu               = s->ilup;
@@ -1650,6 +1664,102 @@ extern "C" HYPRE_Int HYPRE_SchwarzSolve(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HY
    PrecondHints &h = precond_hints();
    schwarz_solve(*s->schwarz, A->A, b->data(), x->data(), h.zero_guess, s->ilu_r, s->ilu_c);
    s->amg_iters = std::max(s->sw_max_iter, 1);
+   HY_CATCH
+}
+
+// ------------------------------------------------------------------------ FSAI
+// HYPRE_FSAI* as driven by hypredrv_FSAICreate (reference src/internal/fsai.c:71-86).  Built (hda_fsai.hip): the static
+// algorithm, algo_type 3 (bj-sfsai), on one rank with HDA_BLOCKS row blocks.  The adaptive algorithms 1 and 2 -- the reference's default --
+// are host algorithms in hypre and are not built; a handle's algo_type starts at 1 as in the reference, so nothing runs another algorithm
+// than the one named.
+namespace hda {
+std::string fsai_refusal(int algo_type, const FsaiParams &p, double tol)
+{
+   if (algo_type != 3)
+   {
+      const char *nm = algo_type == 1 ? "bj-afsai (1)" : algo_type == 2 ? "bj-afsai-omp (2)" : nullptr;
+      return "FSAI: algo_type " + (nm ? std::string(nm) : std::to_string(algo_type)) +
+             " is not implemented on MI355X (the adaptive algorithms, the reference's default, are host algorithms); algo_type bj-sfsai (3), the static "
+             "pattern, is built";
+   }
+   if (tol != 0.0) return "FSAI: tolerance != 0 (a residual test inside the preconditioner) is not implemented; max_iter fixed iterations are";
+   return fsai_params_refusal(p);
+}
+} // namespace hda
+
+extern "C" HYPRE_Int HYPRE_FSAICreate(HYPRE_Solver *solver)
+{
+   if (!solver) return hypre_set_error(HYPRE_ERROR_ARG, "HYPRE_FSAICreate: null output");
+   auto *s = new hypre_Solver_struct();
+   s->kind = HDA_SOLVER_FSAI;
+   *solver = s;
+   return 0;
+}
+// (precon.c:138-154 calls this for whatever handle its table holds: NULL is fine, a handle of another kind is not an FSAI handle)
+extern "C" HYPRE_Int HYPRE_FSAIDestroy(HYPRE_Solver s)
+{
+   if (!s) return 0;
+   if (!is_live_solver(s) || s->kind != HDA_SOLVER_FSAI) return hypre_set_error(HYPRE_ERROR_ARG, "HYPRE_FSAIDestroy: not an FSAI handle");
+   return HYPRE_BoomerAMGDestroy(s);
+}
+HY_SETTER(HYPRE_FSAISetAlgoType, HYPRE_Int, s->fs_algo = v)
+HY_SETTER(HYPRE_FSAISetLocalSolveType, HYPRE_Int, s->fs_ls_type = v)    // adaptive algorithms only: recorded, unused
+HY_SETTER(HYPRE_FSAISetMaxSteps, HYPRE_Int, s->fs_max_steps = v)        // adaptive algorithms only
+HY_SETTER(HYPRE_FSAISetMaxStepSize, HYPRE_Int, s->fs_max_step_size = v) // adaptive algorithms only
+HY_SETTER(HYPRE_FSAISetMaxNnzRow, HYPRE_Int, s->fsaip.max_nnz_row = v)
+HY_SETTER(HYPRE_FSAISetNumLevels, HYPRE_Int, s->fsaip.num_levels = v)
+HY_SETTER(HYPRE_FSAISetEigMaxIters, HYPRE_Int, s->fsaip.eig_max_iters = v)
+HY_SETTER(HYPRE_FSAISetThreshold, HYPRE_Real, s->fsaip.threshold = v)
+HY_SETTER(HYPRE_FSAISetKapTolerance, HYPRE_Real, s->fs_kap_tol = v)     // adaptive algorithms only
+HY_SETTER(HYPRE_FSAISetMaxIterations, HYPRE_Int, s->fsaip.max_iter = v)
+HY_SETTER(HYPRE_FSAISetTolerance, HYPRE_Real, s->fs_tol = v)
+HY_SETTER(HYPRE_FSAISetPrintLevel, HYPRE_Int, s->fs_print_level = v)
+// the same nine numbers for BoomerAMG's FSAI smoother (amg.c:924-932 calls these for EVERY BoomerAMG whatever its smoother: they record
+// and succeed; what they name is checked by HYPRE_BoomerAMGSetup when smooth_type is 4)
+HY_SETTER(HYPRE_BoomerAMGSetFSAIAlgoType, HYPRE_Int, s->fs_algo = v)
+HY_SETTER(HYPRE_BoomerAMGSetFSAILocalSolveType, HYPRE_Int, s->fs_ls_type = v)
+HY_SETTER(HYPRE_BoomerAMGSetFSAIMaxSteps, HYPRE_Int, s->fs_max_steps = v)
+HY_SETTER(HYPRE_BoomerAMGSetFSAIMaxStepSize, HYPRE_Int, s->fs_max_step_size = v)
+HY_SETTER(HYPRE_BoomerAMGSetFSAIMaxNnzRow, HYPRE_Int, s->fsaip.max_nnz_row = v)
+HY_SETTER(HYPRE_BoomerAMGSetFSAINumLevels, HYPRE_Int, s->fsaip.num_levels = v)
+HY_SETTER(HYPRE_BoomerAMGSetFSAIThreshold, HYPRE_Real, s->fsaip.threshold = v)
+HY_SETTER(HYPRE_BoomerAMGSetFSAIEigMaxIters, HYPRE_Int, s->fsaip.eig_max_iters = v)
+HY_SETTER(HYPRE_BoomerAMGSetFSAIKapTolerance, HYPRE_Real, s->fs_kap_tol = v)
+
+extern "C" HYPRE_Int HYPRE_FSAISetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector, HYPRE_ParVector)
+{
+   HY_TRY
+   HDA_REQUIRE(s && is_live_solver(s) && s->kind == HDA_SOLVER_FSAI, "FSAISetup: not an FSAI handle");
+   const std::string why = fsai_refusal(s->fs_algo, s->fsaip, s->fs_tol);
+   if (!why.empty()) throw Error(why);
+   HDA_REQUIRE(Comm::world().size == 1, "FSAI: a world of more than one rank is not implemented (the pattern of a row partition needs off-rank rows of "
+                                        "the power of A); one rank with HDA_BLOCKS row blocks is");
+   if (!have_device()) throw Error("no HIP device visible: the MI355X solve path has no CPU fallback");
+   HDA_REQUIRE(A && A->assembled, "FSAISetup needs an assembled matrix");
+   FsaiParams p = s->fsaip;
+   // "bj": block Jacobi over the ranks in hypre; on one GPU the row blocks play the ranks (HDA_BLOCKS = V, 0 = the setup's choice), as for ILU
+   p.blocks = getenv("HDA_BLOCKS") ? std::max(atoi(getenv("HDA_BLOCKS")), 0) : 1;
+   s->fsai  = std::make_unique<Fsai>();
+   s->fsai->setup(A->A, p);
+   const Fsai &F = *s->fsai;
+   if (F.nblocks > 1 && !getenv("HDA_QUIET"))
+      fprintf(stderr, "[hypredrv_amd] FSAI: %d row blocks (HDA_BLOCKS): no pattern leaves its block, as on %d ranks of the reference\n", F.nblocks, F.nblocks);
+   if (s->fs_print_level >= 1)
+      printf("FSAI (bj-sfsai): num_levels %d, threshold %g, max_nnz_row %d, nnz(G) / n = %.3f, omega = %.6f (%d power steps), fallback rows %d\n", p.num_levels,
+             p.threshold, p.max_nnz_row, F.n ? (double)F.factor().nnz / F.n : 0.0, F.omega, p.eig_max_iters, F.fallback_rows);
+   hda_register_precond_veclen((size_t)std::max(A->A.ncols, A->A.nrows));
+   HY_CATCH
+}
+
+extern "C" HYPRE_Int HYPRE_FSAISolve(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
+{
+   HY_NEED_DEVICE;
+   HY_TRY
+   HDA_REQUIRE(s && s->fsai, "FSAISolve before FSAISetup");
+   x->ensure_device();
+   PrecondHints &h = precond_hints();
+   fsai_solve(*s->fsai, A->A, nullptr, b->data(), x->data(), h.zero_guess, s->ilu_r, s->ilu_c);
+   s->amg_iters = std::max(s->fsaip.max_iter, 1);
    HY_CATCH
 }
 
@@ -2054,21 +2164,8 @@ extern "C" HYPRE_Int HYPRE_BoomerAMGGetComplexities(HYPRE_Solver s, HYPRE_Real *
 // Every HYPRE_* name the reference files of SURVEY 8(a) call (src/internal/{amg,pcg,gmres,ilu,solver,precon}.c) resolves in this
 // library, so an unmodified libHYPREDRV links against it as it is (tests/test_cabi_symbols.py::test_lower_seam_names_resolve,
 // names in tests/golden/hypre_lower_seam_names.txt).  What is outside SURVEY 8 is REFUSED BY NAME: the call sets hypre's error
-// flag with a message and returns non-zero -- never ignored -- with one exception: the FSAI parameter setters, which amg.c:924-932
-// calls for EVERY BoomerAMG whatever its smoother; they record nothing and succeed, and choosing the FSAI smoother itself
-// (HYPRE_BoomerAMGSetSmoothType 4) is what HYPRE_BoomerAMGSetup refuses.
-#define HY_FSAI_PARAM(fn, type) \
-   extern "C" HYPRE_Int fn(HYPRE_Solver s, type) { return s ? 0 : hypre_set_error(HYPRE_ERROR_ARG, #fn ": null solver"); }
-HY_FSAI_PARAM(HYPRE_BoomerAMGSetFSAIAlgoType, HYPRE_Int)
-HY_FSAI_PARAM(HYPRE_BoomerAMGSetFSAILocalSolveType, HYPRE_Int)
-HY_FSAI_PARAM(HYPRE_BoomerAMGSetFSAIMaxSteps, HYPRE_Int)
-HY_FSAI_PARAM(HYPRE_BoomerAMGSetFSAIMaxStepSize, HYPRE_Int)
-HY_FSAI_PARAM(HYPRE_BoomerAMGSetFSAIMaxNnzRow, HYPRE_Int)
-HY_FSAI_PARAM(HYPRE_BoomerAMGSetFSAINumLevels, HYPRE_Int)
-HY_FSAI_PARAM(HYPRE_BoomerAMGSetFSAIThreshold, HYPRE_Real)
-HY_FSAI_PARAM(HYPRE_BoomerAMGSetFSAIEigMaxIters, HYPRE_Int)
-HY_FSAI_PARAM(HYPRE_BoomerAMGSetFSAIKapTolerance, HYPRE_Real)
-#undef HY_FSAI_PARAM
+// flag with a message and returns non-zero -- never ignored.  (The FSAI parameter setters, which amg.c:924-932 calls for EVERY BoomerAMG
+// whatever its smoother, record their values: the FSAI section above.)
 
 #define HY_REFUSED(fn, args, what) \
    extern "C" HYPRE_Int fn args { return hypre_set_error(HYPRE_ERROR_GENERIC, #fn ": " what " is not part of the MI355X solve path (SURVEY 8: out of scope)"); }
@@ -2086,7 +2183,6 @@ HY_REFUSED(HYPRE_ParCSRGMRESSetRefSolution, (HYPRE_Solver, HYPRE_ParVector), "er
 // is not a handle of this library
 #define HY_FOREIGN_DESTROY(fn, what) \
    extern "C" HYPRE_Int fn(HYPRE_Solver s) { return s ? hypre_set_error(HYPRE_ERROR_ARG, #fn ": " what " handles are never created by this library") : 0; }
-HY_FOREIGN_DESTROY(HYPRE_FSAIDestroy, "FSAI")
 HY_FOREIGN_DESTROY(HYPRE_ADSDestroy, "ADS")
 #undef HY_FOREIGN_DESTROY
 

@@ -1663,6 +1663,7 @@ static HYPRE_Int PreconSetupDispatch(HYPRE_Solver cookie, HYPRE_Matrix A, HYPRE_
    HYPRE_Int ierr = (h->precon->kind == HDA_SOLVER_ILU)   ? HYPRE_ILUSetup(h->precon, A, b, x)
                     : (h->precon->kind == HDA_SOLVER_AMS) ? HYPRE_AMSSetup(h->precon, A, b, x)
                     : (h->precon->kind == HDA_SOLVER_SCHWARZ) ? HYPRE_SchwarzSetup(h->precon, A, b, x)
+                    : (h->precon->kind == HDA_SOLVER_FSAI) ? HYPRE_FSAISetup(h->precon, A, b, x)
                     : (h->precon->kind == HDA_SOLVER_MGR) ? HYPRE_MGRSetup(h->precon, A, b, x)
                                                           : HYPRE_BoomerAMGSetup(h->precon, A, b, x);
    if (hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
@@ -1677,6 +1678,7 @@ static HYPRE_Int PreconSolveDispatch(HYPRE_Solver cookie, HYPRE_Matrix A, HYPRE_
    return (h->precon->kind == HDA_SOLVER_ILU)   ? HYPRE_ILUSolve(h->precon, A, b, x)
           : (h->precon->kind == HDA_SOLVER_AMS) ? HYPRE_AMSSolve(h->precon, A, b, x)
           : (h->precon->kind == HDA_SOLVER_SCHWARZ) ? HYPRE_SchwarzSolve(h->precon, A, b, x)
+          : (h->precon->kind == HDA_SOLVER_FSAI) ? HYPRE_FSAISolve(h->precon, A, b, x)
           : (h->precon->kind == HDA_SOLVER_MGR) ? HYPRE_MGRSolve(h->precon, A, b, x)
                                                 : HYPRE_BoomerAMGSolve(h->precon, A, b, x);
 }
@@ -1722,6 +1724,26 @@ static void schwarz_create(const SchwarzArgs &a, HYPRE_Solver *out)
    HYPRE_SchwarzSetTol(p, a.tolerance);
    HYPRE_SchwarzSetPrintLevel(p, a.print_level);
    HYPRE_SchwarzSetLogging(p, a.logging);
+   *out = p;
+}
+
+// hypredrv_FSAICreate (reference src/internal/fsai.c:71-86): same setter sequence
+static void fsai_create(const FsaiArgs &a, HYPRE_Solver *out)
+{
+   HYPRE_Solver p = nullptr;
+   HYPRE_FSAICreate(&p);
+   HYPRE_FSAISetAlgoType(p, a.algo_type);
+   HYPRE_FSAISetLocalSolveType(p, a.ls_type);
+   HYPRE_FSAISetMaxSteps(p, a.max_steps);
+   HYPRE_FSAISetMaxStepSize(p, a.max_step_size);
+   HYPRE_FSAISetMaxNnzRow(p, a.max_nnz_row);
+   HYPRE_FSAISetNumLevels(p, a.num_levels);
+   HYPRE_FSAISetEigMaxIters(p, a.eig_max_iters);
+   HYPRE_FSAISetThreshold(p, a.threshold);
+   HYPRE_FSAISetKapTolerance(p, a.kap_tolerance);
+   HYPRE_FSAISetMaxIterations(p, a.max_iter);
+   HYPRE_FSAISetTolerance(p, a.tolerance);
+   HYPRE_FSAISetPrintLevel(p, a.print_level);
    *out = p;
 }
 
@@ -1788,6 +1810,15 @@ static void amg_create(const AmgArgs &a, HYPRE_Solver *out)
    HYPRE_BoomerAMGSetILUDroptol(p, a.smooth_ilu.droptol);
    HYPRE_BoomerAMGSetILUMaxRowNnz(p, a.smooth_ilu.max_row_nnz);
    HYPRE_BoomerAMGSetILUMaxIter(p, a.smooth_num_sweeps);
+   HYPRE_BoomerAMGSetFSAIAlgoType(p, a.smooth_fsai.algo_type);
+   HYPRE_BoomerAMGSetFSAILocalSolveType(p, a.smooth_fsai.ls_type);
+   HYPRE_BoomerAMGSetFSAIMaxSteps(p, a.smooth_fsai.max_steps);
+   HYPRE_BoomerAMGSetFSAIMaxStepSize(p, a.smooth_fsai.max_step_size);
+   HYPRE_BoomerAMGSetFSAIMaxNnzRow(p, a.smooth_fsai.max_nnz_row);
+   HYPRE_BoomerAMGSetFSAINumLevels(p, a.smooth_fsai.num_levels);
+   HYPRE_BoomerAMGSetFSAIThreshold(p, a.smooth_fsai.threshold);
+   HYPRE_BoomerAMGSetFSAIEigMaxIters(p, a.smooth_fsai.eig_max_iters);
+   HYPRE_BoomerAMGSetFSAIKapTolerance(p, a.smooth_fsai.kap_tolerance);
    HYPRE_BoomerAMGSetNumFunctions(p, a.nodal ? 3 : a.num_functions);
    HYPRE_BoomerAMGSetFilterFunctions(p, a.filter_functions);
    HYPRE_BoomerAMGSetAggNumLevels(p, a.agg_num_levels);
@@ -2052,6 +2083,21 @@ extern "C" uint32_t HYPREDRV_PreconCreate(HYPREDRV_t h)
       consume_hypre_errors();
       return g_err;
    }
+   if (p.method == 3)
+   { // as Schwarz: every value parses, what is not built -- the reference's default algo_type among it -- is refused here by the name of its key
+      const FsaiArgs &a = p.fsai;
+      FsaiParams      q;
+      q.num_levels = a.num_levels; q.threshold = a.threshold; q.max_nnz_row = a.max_nnz_row; q.eig_max_iters = a.eig_max_iters; q.max_iter = a.max_iter;
+      const std::string why = fsai_refusal(a.algo_type, q, a.tolerance);
+      if (!why.empty()) return err_set(ERR_INVALID_PRECON | HYPREDRV_ERROR_UNSUPPORTED_AMD, why);
+      if (Comm::world().size > 1)
+         return err_set(ERR_INVALID_PRECON | HYPREDRV_ERROR_UNSUPPORTED_AMD,
+                        "FSAI: a world of more than one rank is not implemented (the pattern of a row partition needs off-rank rows of the power of A); "
+                        "one rank with HDA_BLOCKS row blocks is");
+      fsai_create(a, &h->precon);
+      consume_hypre_errors();
+      return g_err;
+   }
    if (p.method == 1) return mgr_create(h, p.mgr);
    if (p.method == 4)
    { // as Schwarz: every value parses, what is not built is refused here by the name of its key
@@ -2072,7 +2118,7 @@ extern "C" uint32_t HYPREDRV_PreconCreate(HYPREDRV_t h)
    }
    if (p.method != 0)
       return err_set(ERR_INVALID_PRECON | HYPREDRV_ERROR_UNSUPPORTED_AMD,
-                     "preconditioner '" + p.method_name + "' is not implemented on MI355X yet (BoomerAMG, ILU, MGR, Schwarz and AMS only)");
+                     "preconditioner '" + p.method_name + "' is not implemented on MI355X yet (BoomerAMG, ILU, MGR, Schwarz, AMS and static FSAI only)");
    amg_create(p.amg, &h->precon);
    // hypredrv_AMGSetDofFunc (reference src/internal/amg.c:792-862): the dofmap names the function of
    // every local unknown when its labels fit [0, num_functions); otherwise hypre's interleaved default
@@ -2453,6 +2499,7 @@ extern "C" uint32_t HYPREDRV_PreconApply(HYPREDRV_t h, HYPRE_Vector b, HYPRE_Vec
    if (!h->precon || !h->precon_is_setup) return err_set(ERR_INVALID_PRECON, "PreconApply requires a set-up preconditioner");
    if (h->precon->kind == HDA_SOLVER_ILU) HYPRE_ILUSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
    else if (h->precon->kind == HDA_SOLVER_SCHWARZ) HYPRE_SchwarzSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
+   else if (h->precon->kind == HDA_SOLVER_FSAI) HYPRE_FSAISolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
    else if (h->precon->kind == HDA_SOLVER_AMS) HYPRE_AMSSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
    else if (h->precon->kind == HDA_SOLVER_MGR) HYPRE_MGRSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
    else HYPRE_BoomerAMGSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);

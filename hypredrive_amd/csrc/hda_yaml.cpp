@@ -459,6 +459,20 @@ static void schwarz_fields(Ctx &c, YNode &sec, SchwarzArgs &a)
                  {"ilut_droptol", nullptr, &a.ilut_droptol, nullptr}, {"tolerance", nullptr, &a.tolerance, nullptr}});
 }
 
+// FSAI_FIELDS and the algo_type names of hypredrv_FSAIGetValidValues (reference src/internal/fsai.c:15-27, :45).  Every value parses;
+// what is not built (the adaptive algorithms, a tolerance, numbers out of range) is refused at HYPREDRV_PreconCreate / at setup.
+static const StrMap kFsaiAlgo = {{"bj-afsai", 1}, {"bj-afsai-omp", 2}, {"bj-sfsai", 3}};
+static void fsai_fields(Ctx &c, YNode &sec, FsaiArgs &a)
+{
+   apply_fields(c, sec,
+                {{"max_iter", &a.max_iter, nullptr, nullptr}, {"print_level", &a.print_level, nullptr, nullptr},
+                 {"algo_type", &a.algo_type, nullptr, &kFsaiAlgo}, {"ls_type", &a.ls_type, nullptr, nullptr},
+                 {"max_steps", &a.max_steps, nullptr, nullptr}, {"max_step_size", &a.max_step_size, nullptr, nullptr},
+                 {"max_nnz_row", &a.max_nnz_row, nullptr, nullptr}, {"num_levels", &a.num_levels, nullptr, nullptr},
+                 {"eig_max_iters", &a.eig_max_iters, nullptr, nullptr}, {"threshold", nullptr, &a.threshold, nullptr},
+                 {"kap_tolerance", nullptr, &a.kap_tolerance, nullptr}, {"tolerance", nullptr, &a.tolerance, nullptr}});
+}
+
 // AMS_FIELDS (reference src/internal/ams.c:37-63): 24 keys, numbers only (keys arrive in lower case: alpha_Pmax is alpha_pmax
 // here).  Every value parses; what is not built is refused at HYPREDRV_PreconCreate.
 static void ams_fields(Ctx &c, YNode &sec, AmsArgs &a)
@@ -792,6 +806,7 @@ static void amg_fields(Ctx &c, YNode &sec, AmgArgs &a)
                       {"fsai", "ilu"});
          for (auto &q : k->kids)
             if (q->key == "ilu") ilu_fields(c, *q, a.smooth_ilu);
+            else if (q->key == "fsai") fsai_fields(c, *q, a.smooth_fsai);
       }
       else c.fail(ERR_INVALID_KEY, "unknown key '" + k->key + "' under 'amg'");
    }
@@ -982,6 +997,7 @@ static void parse_precon_body(Ctx &c, YNode &node, std::vector<PreconArgs> &vari
             else if (p.method == 1) mgr_fields(c, *item, v.mgr);
             else if (p.method == 6) schwarz_fields(c, *item, v.schwarz);
             else if (p.method == 4) ams_fields(c, *item, v.ams);
+            else if (p.method == 3) fsai_fields(c, *item, v.fsai);
             variants.push_back(v);
          }
       }
@@ -992,6 +1008,7 @@ static void parse_precon_body(Ctx &c, YNode &node, std::vector<PreconArgs> &vari
          else if (p.method == 1) mgr_fields(c, *ch, p.mgr);
          else if (p.method == 6) schwarz_fields(c, *ch, p.schwarz);
          else if (p.method == 4) ams_fields(c, *ch, p.ams);
+         else if (p.method == 3) fsai_fields(c, *ch, p.fsai);
          variants.push_back(p);
       }
    }

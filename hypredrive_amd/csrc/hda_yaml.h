@@ -78,6 +78,11 @@ struct SchwarzArgs { // Schwarz_args, defaults of src/internal/schwarz.c:20-34 (
           ilut_max_nnz_row = 1000, max_iter = 1, print_level = 0, logging = 0;
    double relax_weight = 1.0, ilut_droptol = 1.0e-2, tolerance = 0.0;
 };
+struct FsaiArgs { // FSAI_args, defaults of src/internal/fsai.c:15-27 (algo_type: 1 bj-afsai, 2 bj-afsai-omp, 3 bj-sfsai)
+   int    max_iter = 1, print_level = 0, algo_type = 1, ls_type = 1, max_steps = 5, max_step_size = 3, max_nnz_row = 15, num_levels = 1,
+          eig_max_iters = 5;
+   double threshold = 1.0e-3, kap_tolerance = 1.0e-3, tolerance = 0.0;
+};
 struct AmsArgs { // AMS_args, defaults of src/internal/ams.c:15-22 (GPU build), :37-63; HYPREDRV_AMD_DEFAULTS=cpu: those of a CPU build
    int    dimension = 3, max_iter = 1, print_level = 0, cycle_type = 1, relax_type = 1, relax_times = 1, proj_freq = 5;
    double tolerance = 0.0, relax_weight = 1.0, omega = 1.0;
@@ -121,6 +126,7 @@ struct AmgArgs { // AMG_args, GPU-branch defaults of src/internal/amg.c:120-238
    // complex smoother
    int    smooth_type = 5, smooth_num_levels = 0, smooth_num_sweeps = 1;
    IluArgs smooth_ilu;
+   FsaiArgs smooth_fsai; // smoother.fsai (amg.c:924-932 forwards nine of its keys; max_iter, tolerance and print_level are not forwarded)
    // The reference picks these defaults at COMPILE time (#ifdef HYPRE_USING_GPU, amg.c:138-146,
    // 183-189); this library is a GPU build.  HYPREDRV_AMD_DEFAULTS=cpu makes it start from the
    // defaults of a CPU build instead (HMIS, hybrid l1 Gauss-Seidel 13/14, no mod_rap2 /
@@ -171,6 +177,7 @@ struct PreconArgs {
    MgrArgs     mgr;
    SchwarzArgs schwarz;
    AmsArgs     ams;
+   FsaiArgs    fsai;
 };
 // preconditioner.reuse (reference src/internal/precon_reuse.c:2280-2567): the static policy
 struct ReuseArgs {

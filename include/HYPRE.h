@@ -340,8 +340,9 @@ HYPRE_Int HYPRE_BoomerAMGGetNumLevels(HYPRE_Solver solver, HYPRE_Int *num_levels
 HYPRE_Int HYPRE_BoomerAMGGetComplexities(HYPRE_Solver solver, HYPRE_Real *grid, HYPRE_Real *op);
 
 /* ---- the rest of the names the reference files of SURVEY 8(a) call (round 5), so that an unmodified libHYPREDRV links as it is.
- * FSAI parameter setters (src/internal/amg.c:924-932 calls them for every BoomerAMG): accepted, nothing recorded -- choosing the FSAI
- * smoother itself (HYPRE_BoomerAMGSetSmoothType 4) is refused by HYPRE_BoomerAMGSetup. */
+ * FSAI parameter setters of the complex smoother (src/internal/amg.c:924-932 calls them for every BoomerAMG): recorded, always 0; with
+ * HYPRE_BoomerAMGSetSmoothType 4 HYPRE_BoomerAMGSetup builds the static FSAI (algo type 3) from them and refuses the adaptive ones (1, 2;
+ * 1 is a handle's default, as in the reference) by name. */
 HYPRE_Int HYPRE_BoomerAMGSetFSAIAlgoType(HYPRE_Solver solver, HYPRE_Int v);
 HYPRE_Int HYPRE_BoomerAMGSetFSAILocalSolveType(HYPRE_Solver solver, HYPRE_Int v);
 HYPRE_Int HYPRE_BoomerAMGSetFSAIMaxSteps(HYPRE_Solver solver, HYPRE_Int v);
@@ -362,7 +363,26 @@ HYPRE_Int HYPRE_BoomerAMGSetInterpVecQMax(HYPRE_Solver solver, HYPRE_Int q_max);
 HYPRE_Int HYPRE_BoomerAMGSetSmoothInterpVectors(HYPRE_Solver solver, HYPRE_Int smooth);
 HYPRE_Int HYPRE_BoomerAMGSetInterpVectors(HYPRE_Solver solver, HYPRE_Int num_vectors, HYPRE_ParVector *interp_vectors);
 HYPRE_Int HYPRE_ParCSRGMRESSetRefSolution(HYPRE_Solver solver, HYPRE_ParVector xref);
+/* ---- FSAI as hypredrv_FSAICreate drives it (src/internal/fsai.c:71-86).  Built on one rank (row blocks: HDA_BLOCKS, as for ILU): algo
+ * type 3 (bj-sfsai, the static pattern as DESIGN section 21 defines it) with max_nnz_row <= 64 and tolerance 0; the adaptive algo types 1
+ * and 2 -- 1 is the default of a new handle, as in the reference -- and everything else are refused by name at Setup.  LocalSolveType,
+ * MaxSteps, MaxStepSize and KapTolerance belong to the adaptive algorithms: recorded and unused.  Destroy accepts NULL and FSAI handles only. */
+HYPRE_Int HYPRE_FSAICreate(HYPRE_Solver *solver);
 HYPRE_Int HYPRE_FSAIDestroy(HYPRE_Solver solver);
+HYPRE_Int HYPRE_FSAISetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_FSAISolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_FSAISetAlgoType(HYPRE_Solver solver, HYPRE_Int algo_type);
+HYPRE_Int HYPRE_FSAISetLocalSolveType(HYPRE_Solver solver, HYPRE_Int local_solve_type);
+HYPRE_Int HYPRE_FSAISetMaxSteps(HYPRE_Solver solver, HYPRE_Int max_steps);
+HYPRE_Int HYPRE_FSAISetMaxStepSize(HYPRE_Solver solver, HYPRE_Int max_step_size);
+HYPRE_Int HYPRE_FSAISetMaxNnzRow(HYPRE_Solver solver, HYPRE_Int max_nnz_row);
+HYPRE_Int HYPRE_FSAISetNumLevels(HYPRE_Solver solver, HYPRE_Int num_levels);
+HYPRE_Int HYPRE_FSAISetEigMaxIters(HYPRE_Solver solver, HYPRE_Int eig_max_iters);
+HYPRE_Int HYPRE_FSAISetThreshold(HYPRE_Solver solver, HYPRE_Real threshold);
+HYPRE_Int HYPRE_FSAISetKapTolerance(HYPRE_Solver solver, HYPRE_Real kap_tolerance);
+HYPRE_Int HYPRE_FSAISetMaxIterations(HYPRE_Solver solver, HYPRE_Int max_iterations);
+HYPRE_Int HYPRE_FSAISetTolerance(HYPRE_Solver solver, HYPRE_Real tolerance);
+HYPRE_Int HYPRE_FSAISetPrintLevel(HYPRE_Solver solver, HYPRE_Int print_level);
 HYPRE_Int HYPRE_AMSDestroy(HYPRE_Solver solver);
 /* ---- AMS as hypredrv_AMSCreate and hypredrv_AMSSetOperators drive it (src/internal/ams.c:78-133).  Built on one rank: cycle types 1,
  * 3, 5 and 7, relax_type 1 (l1-Jacobi), dimension 2 or 3, tol 0, no aggressive levels on the vector space (alpha agg_levels 0);

@@ -43,7 +43,7 @@ typedef struct {
    /* relaxation.chebyshev for relax type 16 (reference src/internal/cheby.c:15-20): order 2, eig_est 10, variant 0, scale 1, fraction 0.3 */
    int      cheby_order, cheby_eig_est, cheby_variant, cheby_scale;
    double   cheby_fraction;
-   /* complex smoother (src/internal/amg.c:899-921), ILU only: bj-iluk, fill 0, natural order on levels < smooth_num_levels */
+   /* complex smoother (src/internal/amg.c:899-921) on levels < smooth_num_levels: ILU (bj-iluk, fill 0, natural order) unless smooth_type below says FSAI */
    int      smooth_num_levels, smooth_num_sweeps;
    int      ilu_tri_solve, ilu_lower_it, ilu_upper_it; /* ILU_args tri_solve / lower_jac_iters / upper_jac_iters (ilu.c:21-23) */
    /* interpolation.restriction_type / restrict_strong_th / restrict_filter_th (src/internal/amg.c:870-874): 0 P^T, 1 air_1, 2 air_2
@@ -55,6 +55,10 @@ typedef struct {
    /* aggressive.P12_max_elements / P12_trunc_factor: truncation of the first stage of the two-stage interpolations (agg_interp_type 5 / 6) */
    int      agg_p12_pmax;
    double   agg_p12_trunc_factor;
+   /* complex smoother type (amg.c:899): 5 ILU (the fields above), 4 static FSAI (bj-sfsai) with the four numbers of
+    * its pattern and scaling: smoother.fsai.num_levels / max_nnz_row / eig_max_iters / threshold */
+   int      smooth_type, fsai_num_levels, fsai_max_nnz_row, fsai_eig_max_iters;
+   double   fsai_threshold;
    /* AMGagg_args (src/internal/amg.c:160-173, forwarded at :938-944): aggressive coarsening on the first agg_num_levels levels
     * (second PMIS pass over the graph of >= agg_num_paths paths of length <= 2); agg_interp_type there: 4 multipass, 5 two-stage
     * mm_extended, 6 two-stage mm_extended+i */
@@ -216,7 +220,21 @@ int hda_schwarz_domains(hda_amg_t h, int *V, int *dom_ptr, int *dom_rows);
 /* info[0..5]: N_ext, nnz of the factors, longest factor row, rows that took the global-memory symbolic path, capacity of the symbolic
  * kernel's LDS table (visited vertices per row), nnz of A; setup_ms (may be NULL): expansion, extraction, symbolic, numeric */
 int hda_schwarz_info(hda_amg_t h, int64_t info[6], double setup_ms[4]);
-/* average device ms of one application (zero guess, vectors resident) of a handle of hda_ilu_create*, hda_schwarz_create or hda_ams_create */
+/* "preconditioner: fsai" (reference src/internal/fsai.c; algo_type bj-sfsai, this project's static pattern: DESIGN section 21): G on the
+ * lower-triangular pattern of the thresholded num_levels-th power of D^-1/2 |A| D^-1/2 (at most max_nnz_row <= 64 entries per row, inside
+ * the row's block: blocks / block_part as hda_ilu_create_blocks), one small SPD solve per row, M^-1 = omega G^T G with omega from
+ * eig_max_iters power steps (0: omega = 1); one application is max_iter iterations x += M^-1 (b - A x).  The handle is accepted by the
+ * Krylov entries, hda_amg_vcycle and hda_precond_time as an ILU handle is. */
+int hda_fsai_create(hda_csr_t A, int num_levels, double threshold, int max_nnz_row, int eig_max_iters, int max_iter, int blocks,
+                    const int64_t *block_part, hda_amg_t *out);
+/* borrowed view of G (rows column-sorted, diagonal last).  level < 0: a handle of hda_fsai_create; level >= 0: the FSAI smoother of
+ * that AMG level */
+int hda_fsai_factor(hda_amg_t h, int level, hda_csr_t *out);
+/* info[0..8]: rows, nnz(G), rows that fell back to 1 / sqrt(a_ii), row blocks, rows solved with 4 / 8 / 16 / 32 / 64 lanes; vals (may
+ * be NULL): omega, algorithmic bytes of one application, setup ms of pattern / local systems / transpose and plans / omega */
+int hda_fsai_info(hda_amg_t h, int level, int64_t info[9], double vals[6]);
+/* average device ms of one application (zero guess, vectors resident) of a handle of hda_ilu_create*, hda_schwarz_create, hda_ams_create
+ * or hda_fsai_create */
 int hda_precond_time(hda_amg_t h, int reps, double *avg_ms);
 /* "preconditioner: ams" (reference src/internal/ams.c): the auxiliary-space Maxwell preconditioner on one rank.
  * A is n_e x n_e, G (n_e x n_v) the discrete gradient, c0 / c1 / c2 host vectors of n_v vertex coordinates (c2 is not read when

@@ -16,7 +16,10 @@ iteration count == oracle's.  bench.py carries them as budgeted extras; `python 
                   blocks HDA_BLOCKS gives: setup ms by phase, ms per application, iterations (`python tools/side_configs.py schwarz 128`)
   ams N           not a BASELINE config: PCG + AMS (examples/maxwell-ams.yml) on the definite Maxwell operator of
                   tests/ams_reference.py (maxwell_fd, mass coefficient 1e-3) at N^3 nodes: iterations, ms per solve, setup seconds, the
-                  dominant kernel's bytes / time (`python tools/side_configs.py ams 64`)"""
+                  dominant kernel's bytes / time (`python tools/side_configs.py ams 64`)
+  fsai N          not a BASELINE config: PCG + static FSAI (the preconditioner block of examples/ex1-fsai-static.yml) on
+                  the N^3 7-point Laplacian: iterations, ms per solve, setup seconds, nnz(G) / n, and the application's bytes / time
+                  beside the l1-Jacobi sweep on the same A (`python tools/side_configs.py fsai 128`)"""
 import json
 import os
 import sys
@@ -236,6 +239,50 @@ def pcg_ams(hh, n=64, steps=3, warmup=1):
     return out
 
 
+YAML_FSAI = ("solver:\n  pcg:\n    relative_tol: 1.0e-8\n    max_iter: 1000\npreconditioner:\n  fsai:\n    algo_type: bj-sfsai\n    num_levels: 2\n"
+             "    max_nnz_row: 15\n    threshold: 1.0e-3\n    eig_max_iters: 5\n")
+
+
+def pcg_fsai(hh, n=128, steps=3, warmup=1, reps=20):
+    """PCG(1e-8) + static FSAI (num_levels 2, max_nnz_row 15) through HYPREDRV_LinearSolverSetup / Apply on the generator's n^3 7-point
+    Laplacian; then, on a handle of its own on the same operator, one application (two products with G and G^T) beside one l1-Jacobi sweep."""
+    from hypredrive_amd import hypredrv as hd
+    N = n ** 3
+    h = hd.Hypredrv(YAML_FSAI)
+    h.set_laplacian7((n, n, n))
+    setup = _timed(hh, h, steps, warmup)
+    ms, last = _solves(hh, h, steps, warmup)
+    h.destroy_solver()
+    h.close()
+    A = hh.lap7(n, n, n, want_rhs=False)
+    hh.Fsai(A, 2, 1e-3, 15, 5)  # the first setup of a shape also pays for the allocator
+    hh.sync()
+    t0 = time.perf_counter()
+    F = hh.Fsai(A, 2, 1e-3, 15, 5)
+    hh.sync()
+    handle_setup_ms = (time.perf_counter() - t0) * 1e3
+    info = F.info()
+    a_ms = hh.precond_time(F, reps)
+    j_ms, j_by = hh.time_kernel(1, A, reps=reps)
+    a_by = info["apply_bytes"]
+    out = {"what": f"PCG + static FSAI (bj-sfsai, num_levels 2, max_nnz_row 15, threshold 1e-3, 5 power steps) on the {n}^3 7-point Laplacian; "
+                   "parity unpinned (the static pattern is this project's definition, DESIGN section 21)",
+           "rows": N, "iters": last["iters"], "converged": last["converged"], "final_rel": last["final_rel"], "ms_per_step": ms,
+           "value": N / (ms * 1e-3), "unit": "DOF/s", "setup_s": setup[1] * 1e-3, "setup_cold_s": setup[0] * 1e-3,
+           "nnz_G_per_row": info["nnz_factor"] / N, "omega": info["omega"], "fallback_rows": info["fallback_rows"],
+           "lane_class_rows": {str(k): v for k, v in info["class_rows"].items()}, "handle_setup_ms": handle_setup_ms,
+           "setup_phases_ms": info["setup_ms"],
+           "apply": {"kernel": "z = omega G^T (G r): two products", "bytes": a_by, "avg_ms": a_ms, "gbs": a_by / a_ms / 1e6 if a_ms else None,
+                     "frac": a_by / a_ms / 1e6 / HBM_PEAK_GBS if a_ms else None},
+           "l1_jacobi_sweep": {"kernel": "l1-Jacobi sweep on the same A", "bytes": j_by, "avg_ms": j_ms, "gbs": j_by / j_ms / 1e6 if j_ms else None,
+                               "frac": j_by / j_ms / 1e6 / HBM_PEAK_GBS if j_ms else None}}
+    kp = hh.KrylovParams.default(rtol=1e-8, max_iter=1000)
+    rj = hh.pcg(A, np.ones(N), None, kp)
+    out["unpreconditioned_pcg_iters_b_ones"] = rj["iters"]
+    out["fsai_pcg_iters_b_ones"] = hh.pcg(A, np.ones(N), F, kp)["iters"]
+    return out
+
+
 if __name__ == "__main__":
     import hypredrive_amd as hh
     which = sys.argv[1] if len(sys.argv) > 1 else "mgr"
@@ -243,6 +290,8 @@ if __name__ == "__main__":
         print(json.dumps(gmres_schwarz(hh, int(sys.argv[2]) if len(sys.argv) > 2 else 128)))
     elif which == "ams":
         print(json.dumps(pcg_ams(hh, int(sys.argv[2]) if len(sys.argv) > 2 else 64)))
+    elif which == "fsai":
+        print(json.dumps(pcg_fsai(hh, int(sys.argv[2]) if len(sys.argv) > 2 else 128)))
     elif which == "mgr":
         print(json.dumps(gmres_mgr(hh, int(sys.argv[2]) if len(sys.argv) > 2 else 512)))
     else:
