@@ -202,8 +202,25 @@ class Ilu {
    int blocks_used() const { return bpart.empty() ? 1 : (int)bpart.size() - 1; }
 };
 
-void ilu_solve(Ilu &F, const DCsr &A, const HaloPlan *halo, const double *b, double *x, bool zero_guess, DArray<double> &r,
-               DArray<double> &c); // max_iter iterations x += M^-1 (b - A x)
+// `iters` iterations x += M^-1 (b - A x) for any M with apply(r, z): hypre's ILU / Schwarz / FSAI solve as hypredrive uses it
+// (preconditioner, smoother or stand-alone).  From a zero guess the first iteration skips the product.  r, c: work vectors, grown
+// here.  x must have room for A's ghost columns when A is a row block (halo != null).
+template <class M>
+void stationary_solve(M &m, const DCsr &A, const HaloPlan *halo, const double *b, double *x, bool zero_guess, int iters, DArray<double> &r,
+                      DArray<double> &c)
+{
+   const int n = A.nrows;
+   if (r.size() < (size_t)std::max(n, 1)) r.alloc((size_t)std::max(n, 1));
+   if (c.size() < (size_t)std::max(n, 1)) c.alloc((size_t)std::max(n, 1));
+   for (int it = 0; it < iters; it++)
+   {
+      if (zero_guess && it == 0) { m.apply(b, x); continue; } // b - A*0 = b exactly
+      if (halo) halo_exchange(*halo, x);
+      residual(A, x, b, r.data());
+      m.apply(r.data(), c.data());
+      axpy(n, 1.0, c.data(), x);
+   }
+}
 
 // overlapping Schwarz with ILU(k) subdomain solves (hda_schwarz.hip): V contiguous row blocks grown by `overlap`
 // layers of the stored pattern of A, ILU(fill) of every A[Omega_b, Omega_b], z = w * (restricted | additive) combination of the
@@ -238,7 +255,6 @@ class Schwarz {
    DArray<int>      copy_ptr, copy_pos; // n + 1 / n_ext: the positions that hold row i, ascending subdomain
    DArray<double>   r_ext, y_ext;
 };
-void schwarz_solve(Schwarz &S, const DCsr &A, const double *b, double *x, bool zero_guess, DArray<double> &r, DArray<double> &c);
 
 // static factorised sparse approximate inverse (hda_fsai.hip): the algo_type bj-sfsai of the reference's FSAI_args
 // (src/internal/fsai.c) as this project defines it -- G on the lower-triangular pattern of a thresholded power of the scaled |A|, one
@@ -271,9 +287,6 @@ class Fsai {
    DCsr           G, GT;
    DArray<double> work;
 };
-// max_iter (or iters > 0) iterations x += M^-1 (b - A x)
-void fsai_solve(Fsai &F, const DCsr &A, const HaloPlan *halo, const double *b, double *x, bool zero_guess, DArray<double> &r, DArray<double> &c,
-                int iters = 0);
 
 // PCG <-> preconditioner: a V-cycle from a zero guess that opens with the Jacobi sweep z0 = dinv .* r on level 0 lets its caller do
 // that multiplication where r is produced (PCG's update kernel: one pass over r and one launch less per iteration).  Thread-local,

@@ -3940,7 +3940,7 @@ void Amg::relax(int l, int type, const double *dinv, const double *b, double *&c
    if (levels[(size_t)l].fsai)
    { // the same with the static FSAI (one rank)
       AmgLevel &lv = levels[(size_t)l];
-      fsai_solve(*lv.fsai, A, nullptr, b, cur, zero_guess, lv.ilu_r, lv.ilu_c);
+      stationary_solve(*lv.fsai, A, nullptr, b, cur, zero_guess, std::max(lv.fsai->prm.max_iter, 1), lv.ilu_r, lv.ilu_c);
       if (dot_slot >= 0) dot(A.nrows, b, cur, dot_slot);
       return;
    }

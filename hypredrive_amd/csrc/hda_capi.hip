@@ -1,7 +1,7 @@
 // hda_capi.hip -- kernel-level C ABI (include/hypredrv_amd.h).  Host buffers in / out.
 #include "../../include/hypredrv_amd.h"
 
-#include "hda_krylov.h"
+#include "hda_precond.h"
 #include "hda_comm.h"
 #include "hda_hypre.h"
 
@@ -21,14 +21,7 @@ struct hda_csr_s {
    const DCsr    &get() const { return ref ? *ref : m; }
 };
 struct hda_amg_s {
-   Amg                                    *amg = nullptr; // the hierarchy: owned_amg.get(), or borrowed from a HYPREDRV object
-   std::unique_ptr<Amg>                    owned_amg;
-   std::unique_ptr<Ilu>                    ilu; // handle made by hda_ilu_create: the preconditioner is one ILU solve
-   std::unique_ptr<Mgr>                    mgr; // handle made by hda_mgr_create: the preconditioner is one MGR solve
-   std::unique_ptr<Schwarz>                schwarz; // handle made by hda_schwarz_create: one Schwarz solve (work vectors: ilu_r / ilu_c)
-   std::unique_ptr<Ams>                    ams; // handle made by hda_ams_create: one AMS application
-   std::unique_ptr<Fsai>                   fsai; // handle made by hda_fsai_create: one FSAI solve (work vectors: ilu_r / ilu_c)
-   DArray<double>                          ilu_r, ilu_c;
+   Precond                                 pc; // what hda_*_create made: a hierarchy (owned, or borrowed from a HYPREDRV object) or one of the other kinds
    hda_csr_t                               A = nullptr;
    std::vector<std::unique_ptr<hda_csr_s>> views;
 };
@@ -742,29 +735,20 @@ extern "C" int hda_air_restriction(hda_csr_t A, const int *cf, int distance, dou
 
 // ------------------------------------------------------------------ hierarchy
 
-extern "C" int hda_amg_create(const hda_amg_params *p, hda_csr_t A, hda_amg_t *out)
-{
-   HDA_TRY
-   auto h = std::make_unique<hda_amg_s>();
-   h->owned_amg = std::make_unique<Amg>(to_params(p));
-   h->amg       = h->owned_amg.get();
-   h->A         = A;
-   h->amg->setup(A->get());
-   *out = h.release();
-   HDA_CATCH
-}
 extern "C" int hda_amg_create_dof(const hda_amg_params *p, hda_csr_t A, const int *dof_func, hda_amg_t *out)
 {
    HDA_TRY
    auto h = std::make_unique<hda_amg_s>();
-   h->owned_amg = std::make_unique<Amg>(to_params(p));
-   h->amg       = h->owned_amg.get();
-   h->A         = A;
-   if (dof_func) h->amg->dof_func0.assign(dof_func, dof_func + A->get().nrows);
-   h->amg->setup(A->get());
+   h->pc.owned_amg = std::make_unique<Amg>(to_params(p));
+   h->pc.amg       = h->pc.owned_amg.get();
+   h->pc.kind      = Precond::AMG;
+   h->A            = A;
+   if (dof_func) h->pc.amg->dof_func0.assign(dof_func, dof_func + A->get().nrows);
+   h->pc.amg->setup(A->get());
    *out = h.release();
    HDA_CATCH
 }
+extern "C" int hda_amg_create(const hda_amg_params *p, hda_csr_t A, hda_amg_t *out) { return hda_amg_create_dof(p, A, nullptr, out); }
 extern "C" int hda_amg_destroy(hda_amg_t h)
 {
    if (!h) return HDA_OK;
@@ -772,43 +756,36 @@ extern "C" int hda_amg_destroy(hda_amg_t h)
    delete h;
    return HDA_OK;
 }
-extern "C" int hda_amg_num_levels(hda_amg_t h) { return (h && h->amg) ? h->amg->num_levels() : 0; }
+extern "C" int hda_amg_num_levels(hda_amg_t h) { return (h && h->pc.amg) ? h->pc.amg->num_levels() : 0; }
 
 // "preconditioner: ilu" (reference src/internal/ilu.c): a handle the Krylov entry points accept in place of a hierarchy
-extern "C" int hda_ilu_create(hda_csr_t A, int max_iter, int tri_solve, int lower_it, int upper_it, hda_amg_t *out)
-{
-   HDA_TRY
-   auto h = std::make_unique<hda_amg_s>();
-   h->A   = A;
-   h->ilu = std::make_unique<Ilu>();
-   IluParams p;
-   p.max_iter = max_iter; p.tri_solve = tri_solve; p.lower_it = lower_it; p.upper_it = upper_it;
-   h->ilu->setup(A->get(), p);
-   *out = h.release();
-   HDA_CATCH
-}
-// the same on V row blocks (IluParams::blocks: bj-iluk at np = V; block_part = V + 1 row starts or NULL for hypre's even split)
+// on V row blocks (IluParams::blocks: bj-iluk at np = V; block_part = V + 1 row starts or NULL for hypre's even split)
 extern "C" int hda_ilu_create_blocks(hda_csr_t A, int max_iter, int tri_solve, int lower_it, int upper_it, int blocks, const int64_t *block_part,
                                      hda_amg_t *out)
 {
    HDA_TRY
    auto h = std::make_unique<hda_amg_s>();
-   h->A   = A;
-   h->ilu = std::make_unique<Ilu>();
+   h->A       = A;
+   h->pc.kind = Precond::ILU;
+   h->pc.ilu  = std::make_unique<Ilu>();
    IluParams p;
    p.max_iter = max_iter; p.tri_solve = tri_solve; p.lower_it = lower_it; p.upper_it = upper_it;
    p.blocks   = blocks;
    if (block_part && blocks > 1) p.block_part.assign(block_part, block_part + blocks + 1);
-   h->ilu->setup(A->get(), p);
+   h->pc.ilu->setup(A->get(), p);
    *out = h.release();
    HDA_CATCH
+}
+extern "C" int hda_ilu_create(hda_csr_t A, int max_iter, int tri_solve, int lower_it, int upper_it, hda_amg_t *out)
+{ // one block
+   return hda_ilu_create_blocks(A, max_iter, tri_solve, lower_it, upper_it, 1, nullptr, out);
 }
 extern "C" int hda_ilu_blocks(hda_amg_t h, int level)
 {
    if (!h) return 0;
-   if (level < 0) return h->ilu ? h->ilu->blocks_used() : 0;
-   if (!h->amg || level >= h->amg->num_levels() || !h->amg->level(level).ilu) return 0;
-   return h->amg->level(level).ilu->blocks_used();
+   if (level < 0) return h->pc.ilu ? h->pc.ilu->blocks_used() : 0;
+   if (!h->pc.amg || level >= h->pc.amg->num_levels() || !h->pc.amg->level(level).ilu) return 0;
+   return h->pc.amg->level(level).ilu->blocks_used();
 }
 // "preconditioner: schwarz" (reference src/internal/schwarz.c): RAS / AS with ILU(k) subdomain solves (hda_schwarz.hip)
 extern "C" int hda_schwarz_create(hda_csr_t A, int variant, int overlap, int fill, int blocks, const int64_t *block_part, int max_iter,
@@ -818,20 +795,21 @@ extern "C" int hda_schwarz_create(hda_csr_t A, int variant, int overlap, int fil
    HDA_REQUIRE(A && out, "hda_schwarz_create: null argument");
    auto h     = std::make_unique<hda_amg_s>();
    h->A       = A;
-   h->schwarz = std::make_unique<Schwarz>();
+   h->pc.kind    = Precond::SCHWARZ;
+   h->pc.schwarz = std::make_unique<Schwarz>();
    SchwarzParams p;
    p.variant = variant; p.overlap = overlap; p.fill = fill; p.max_iter = max_iter; p.weight = weight;
    p.blocks  = blocks;
    if (block_part && blocks > 1) p.block_part.assign(block_part, block_part + blocks + 1);
-   h->schwarz->setup(A->get(), p);
+   h->pc.schwarz->setup(A->get(), p);
    *out = h.release();
    HDA_CATCH
 }
 extern "C" int hda_schwarz_domains(hda_amg_t h, int *V, int *dom_ptr, int *dom_rows)
 {
    HDA_TRY
-   HDA_REQUIRE(h && h->schwarz, "not a Schwarz handle");
-   const Schwarz &S = *h->schwarz;
+   HDA_REQUIRE(h && h->pc.schwarz, "not a Schwarz handle");
+   const Schwarz &S = *h->pc.schwarz;
    if (V) *V = S.num_domains();
    if (dom_ptr)
    {
@@ -848,8 +826,8 @@ extern "C" int hda_schwarz_domains(hda_amg_t h, int *V, int *dom_ptr, int *dom_r
 extern "C" int hda_schwarz_info(hda_amg_t h, int64_t info[6], double setup_ms[4])
 {
    HDA_TRY
-   HDA_REQUIRE(h && h->schwarz && info, "not a Schwarz handle");
-   const Schwarz &S = *h->schwarz;
+   HDA_REQUIRE(h && h->pc.schwarz && info, "not a Schwarz handle");
+   const Schwarz &S = *h->pc.schwarz;
    info[0] = S.n_ext; info[1] = S.factors().nnz; info[2] = S.longest_row; info[3] = S.global_rows; info[4] = kSchwarzLdsRows; info[5] = S.nnz_A;
    if (setup_ms)
       for (int q = 0; q < 4; q++) setup_ms[q] = S.setup_ms[q];
@@ -862,22 +840,23 @@ extern "C" int hda_fsai_create(hda_csr_t A, int num_levels, double threshold, in
    HDA_TRY
    HDA_REQUIRE(A && out, "hda_fsai_create: null argument");
    auto h  = std::make_unique<hda_amg_s>();
-   h->A    = A;
-   h->fsai = std::make_unique<Fsai>();
+   h->A       = A;
+   h->pc.kind = Precond::FSAI;
+   h->pc.fsai = std::make_unique<Fsai>();
    FsaiParams p;
    p.num_levels = num_levels; p.threshold = threshold; p.max_nnz_row = max_nnz_row; p.eig_max_iters = eig_max_iters; p.max_iter = max_iter;
    p.blocks = blocks;
    if (block_part && blocks > 1) p.block_part.assign(block_part, block_part + blocks + 1);
-   h->fsai->setup(A->get(), p);
+   h->pc.fsai->setup(A->get(), p);
    *out = h.release();
    HDA_CATCH
 }
 static Fsai *fsai_of(hda_amg_t h, int level)
 {
    HDA_REQUIRE(h, "null handle");
-   if (level < 0) return h->fsai.get();
-   HDA_REQUIRE(h->amg && level < h->amg->num_levels(), "level out of range");
-   return h->amg->level(level).fsai.get();
+   if (level < 0) return h->pc.fsai.get();
+   HDA_REQUIRE(h->pc.amg && level < h->pc.amg->num_levels(), "level out of range");
+   return h->pc.amg->level(level).fsai.get();
 }
 extern "C" int hda_fsai_factor(hda_amg_t h, int level, hda_csr_t *out)
 {
@@ -936,20 +915,21 @@ extern "C" int hda_ams_create(hda_csr_t A, hda_csr_t G, const double *c0, const 
       dc[k] = c[k].data();
    }
    auto h = std::make_unique<hda_amg_s>();
-   h->A   = A;
-   h->ams = std::make_unique<Ams>();
-   h->ams->setup(A->get(), g, dc, p);
+   h->A       = A;
+   h->pc.kind = Precond::AMS;
+   h->pc.ams  = std::make_unique<Ams>();
+   h->pc.ams->setup(A->get(), g, dc, p);
    *out = h.release();
    HDA_CATCH
 }
 extern "C" int hda_ams_matrix(hda_amg_t h, int which, hda_csr_t *out)
 {
    HDA_TRY
-   HDA_REQUIRE(h && h->ams && out, "not an AMS handle");
+   HDA_REQUIRE(h && h->pc.ams && out, "not an AMS handle");
    HDA_REQUIRE(which >= 0 && which <= 2, "which: 0 Pi, 1 G^T A G, 2 Pi^T A Pi");
    auto v      = std::make_unique<hda_csr_s>();
    v->borrowed = true;
-   v->ref      = (which == 0) ? &h->ams->pi() : (which == 1) ? &h->ams->a_g() : &h->ams->a_pi();
+   v->ref      = (which == 0) ? &h->pc.ams->pi() : (which == 1) ? &h->pc.ams->a_g() : &h->pc.ams->a_pi();
    *out        = v.get();
    h->views.push_back(std::move(v));
    HDA_CATCH
@@ -957,8 +937,8 @@ extern "C" int hda_ams_matrix(hda_amg_t h, int which, hda_csr_t *out)
 extern "C" int hda_ams_info(hda_amg_t h, int64_t info[8], double ms[5])
 {
    HDA_TRY
-   HDA_REQUIRE(h && h->ams && info, "not an AMS handle");
-   Ams &S  = *h->ams;
+   HDA_REQUIRE(h && h->pc.ams && info, "not an AMS handle");
+   Ams &S  = *h->pc.ams;
    info[0] = S.n_e; info[1] = S.n_v; info[2] = S.pi().nnz; info[3] = S.a_g().nnz; info[4] = S.a_pi().nnz;
    info[5] = S.fixed_rows[0]; info[6] = S.fixed_rows[1]; info[7] = 256 * S.b_g().num_levels() + S.b_pi().num_levels();
    if (ms)
@@ -971,19 +951,14 @@ extern "C" int hda_ams_info(hda_amg_t h, int64_t info[8], double ms[5])
 extern "C" int hda_precond_time(hda_amg_t h, int reps, double *avg_ms)
 {
    HDA_TRY
-   HDA_REQUIRE(h && (h->ilu || h->schwarz || h->ams || h->fsai) && avg_ms && reps > 0,
+   HDA_REQUIRE(h && h->pc.kind != Precond::NONE && !h->pc.amg && avg_ms && reps > 0,
                "hda_precond_time: an ILU, Schwarz, AMS or FSAI handle and reps > 0 are needed");
    Context       &ctx = Context::get();
    const DCsr    &m   = h->A->get();
-   const size_t   nv  = (size_t)std::max(std::max(m.ncols, m.nrows), 1);
+   const size_t   nv  = h->pc.vec_len(m);
    DArray<double> b(nv), x(nv);
    fill((int)nv, 0.5, b.data());
-   auto launch = [&]() {
-      if (h->ams) h->ams->apply(b.data(), x.data());
-      else if (h->fsai) fsai_solve(*h->fsai, m, nullptr, b.data(), x.data(), true, h->ilu_r, h->ilu_c);
-      else if (h->schwarz) schwarz_solve(*h->schwarz, m, b.data(), x.data(), true, h->ilu_r, h->ilu_c);
-      else ilu_solve(*h->ilu, m, nullptr, b.data(), x.data(), true, h->ilu_r, h->ilu_c);
-   };
+   auto launch = [&]() { h->pc.solve(m, nullptr, b.data(), x.data(), true); };
    for (int w = 0; w < 3; w++) launch();
    hipEvent_t e0, e1;
    HDA_HIP(hipEventCreate(&e0));
@@ -1055,8 +1030,9 @@ extern "C" int hda_mgr_create(hda_csr_t A, const int *labels, int nlevels, const
    auto h = std::make_unique<hda_amg_s>();
    h->A   = A;
    p.keep_blocks = true; // (this handle serves the test entry hda_mgr_blk_inverses)
-   h->mgr = std::make_unique<Mgr>(p);
-   h->mgr->setup(A->get(), std::vector<int>(labels, labels + A->get().nrows));
+   h->pc.kind = Precond::MGR;
+   h->pc.mgr  = std::make_unique<Mgr>(p);
+   h->pc.mgr->setup(A->get(), std::vector<int>(labels, labels + A->get().nrows));
    *out = h.release();
    HDA_CATCH
 }
@@ -1064,10 +1040,10 @@ extern "C" int hda_mgr_create(hda_csr_t A, const int *labels, int nlevels, const
 extern "C" int hda_mgr_matrix(hda_amg_t h, int level, int which, hda_csr_t *out)
 {
    HDA_TRY
-   HDA_REQUIRE(h && h->mgr, "not an MGR handle");
+   HDA_REQUIRE(h && h->pc.mgr, "not an MGR handle");
    auto v      = std::make_unique<hda_csr_s>();
    v->borrowed = true;
-   v->ref      = &h->mgr->matrix(level, which);
+   v->ref      = &h->pc.mgr->matrix(level, which);
    *out        = v.get();
    h->views.push_back(std::move(v));
    HDA_CATCH
@@ -1075,8 +1051,8 @@ extern "C" int hda_mgr_matrix(hda_amg_t h, int level, int which, hda_csr_t *out)
 extern "C" int hda_mgr_blk_inverses(hda_amg_t h, int level, int tier, double *out, int *b, int *nf)
 {
    HDA_TRY
-   HDA_REQUIRE(h && h->mgr && b && nf, "not an MGR handle");
-   const std::vector<double> v = h->mgr->block_inverses(level, tier, *b, *nf);
+   HDA_REQUIRE(h && h->pc.mgr && b && nf, "not an MGR handle");
+   const std::vector<double> v = h->pc.mgr->block_inverses(level, tier, *b, *nf);
    if (out && !v.empty()) std::copy(v.begin(), v.end(), out);
    HDA_CATCH
 }
@@ -1084,8 +1060,8 @@ extern "C" int hda_mgr_blk_inverses(hda_amg_t h, int level, int tier, double *ou
 extern "C" int hda_mgr_setup_ms(hda_amg_t h, double *out, int *n)
 {
    HDA_TRY
-   HDA_REQUIRE(h && h->mgr && n, "not an MGR handle");
-   const std::vector<double> &v = h->mgr->level_ms;
+   HDA_REQUIRE(h && h->pc.mgr && n, "not an MGR handle");
+   const std::vector<double> &v = h->pc.mgr->level_ms;
    if (out) std::copy(v.begin(), v.begin() + std::min<size_t>(v.size(), (size_t)std::max(*n, 0)), out);
    *n = (int)v.size();
    HDA_CATCH
@@ -1096,20 +1072,20 @@ extern "C" int hda_ilu_factors(hda_amg_t h, int level, hda_csr_t *out)
 {
    HDA_TRY
    const Ilu *F = nullptr;
-   if (level < 0 && h->schwarz)
+   if (level < 0 && h->pc.schwarz)
    { // the block-diagonal factors of all subdomains, extended numbering
       auto v      = std::make_unique<hda_csr_s>();
       v->borrowed = true;
-      v->ref      = &h->schwarz->factors();
+      v->ref      = &h->pc.schwarz->factors();
       *out        = v.get();
       h->views.push_back(std::move(v));
       return HDA_OK;
    }
-   if (level < 0) F = h->ilu.get();
+   if (level < 0) F = h->pc.ilu.get();
    else
    {
-      HDA_REQUIRE(h->amg && level < h->amg->num_levels(), "level out of range");
-      F = h->amg->level(level).ilu.get();
+      HDA_REQUIRE(h->pc.amg && level < h->pc.amg->num_levels(), "level out of range");
+      F = h->pc.amg->level(level).ilu.get();
    }
    HDA_REQUIRE(F, "no ILU factorisation on this handle / level");
    auto v      = std::make_unique<hda_csr_s>();
@@ -1123,15 +1099,15 @@ extern "C" int hda_ilu_factors(hda_amg_t h, int level, hda_csr_t *out)
 extern "C" int hda_amg_level_matrix(hda_amg_t h, int level, int which, hda_csr_t *out)
 {
    HDA_TRY
-   HDA_REQUIRE(level >= 0 && level < h->amg->num_levels(), "level out of range");
+   HDA_REQUIRE(level >= 0 && level < h->pc.amg->num_levels(), "level out of range");
    const DCsr *m = nullptr;
-   if (which == 0) m = &h->amg->level_A(level);
+   if (which == 0) m = &h->pc.amg->level_A(level);
    else
    {
-      HDA_REQUIRE(level < h->amg->num_levels() - 1, "no transfer operator on the coarsest level");
+      HDA_REQUIRE(level < h->pc.amg->num_levels() - 1, "no transfer operator on the coarsest level");
       HDA_REQUIRE(which >= 1 && which <= 3, "which: 0 operator, 1 P, 2 R, 3 the folded up-leg operator");
-      HDA_REQUIRE(which != 3 || h->amg->level_folded(level), "the up leg of this level is not folded");
-      m = (which == 1) ? &h->amg->level(level).P : (which == 2) ? &h->amg->level(level).R : &h->amg->level(level).Pt;
+      HDA_REQUIRE(which != 3 || h->pc.amg->level_folded(level), "the up leg of this level is not folded");
+      m = (which == 1) ? &h->pc.amg->level(level).P : (which == 2) ? &h->pc.amg->level(level).R : &h->pc.amg->level(level).Pt;
    }
    auto v      = std::make_unique<hda_csr_s>();
    v->borrowed = true;
@@ -1143,9 +1119,9 @@ extern "C" int hda_amg_level_matrix(hda_amg_t h, int level, int which, hda_csr_t
 extern "C" int hda_amg_fold_sweep(hda_amg_t h, int level, const double *dinv, const double *t, const double *e, const double *u, double *out)
 {
    HDA_TRY
-   HDA_REQUIRE(h && h->amg && dinv && t && e && u && out, "hda_amg_fold_sweep: null argument");
-   HDA_REQUIRE(h->amg->level_folded(level), "the up leg of this level is not folded");
-   const DCsr    &A = h->amg->level_A(level), &M = h->amg->level(level).Pt;
+   HDA_REQUIRE(h && h->pc.amg && dinv && t && e && u && out, "hda_amg_fold_sweep: null argument");
+   HDA_REQUIRE(h->pc.amg->level_folded(level), "the up leg of this level is not folded");
+   const DCsr    &A = h->pc.amg->level_A(level), &M = h->pc.amg->level(level).Pt;
    DArray<double> dd, dt, de, du, dout((size_t)M.nrows);
    dd.upload(dinv, (size_t)M.nrows);
    dt.upload(t, (size_t)M.nrows);
@@ -1161,13 +1137,13 @@ extern "C" int hda_amg_fold_sweep(hda_amg_t h, int level, const double *dinv, co
 extern "C" int hda_amg_level0_sweep(hda_amg_t h, int dir, const double *b, const double *x, double *out, double *dot, int *by_class)
 {
    HDA_TRY
-   HDA_REQUIRE(h && h->amg && b && x && out && by_class, "hda_amg_level0_sweep: null argument");
-   const DCsr    &A = h->amg->level_A(0);
+   HDA_REQUIRE(h && h->pc.amg && b && x && out && by_class, "hda_amg_level0_sweep: null argument");
+   const DCsr    &A = h->pc.amg->level_A(0);
    DArray<double> db, dx((size_t)std::max(A.ncols, A.nrows)), dout((size_t)A.nrows);
    db.upload(b, (size_t)A.nrows);
    dx.zero();
    dx.upload(x, (size_t)A.nrows);
-   *by_class = h->amg->level0_sweep(dir, db.data(), dx.data(), dout.data(), dot ? 0 : -1) ? 1 : 0;
+   *by_class = h->pc.amg->level0_sweep(dir, db.data(), dx.data(), dout.data(), dot ? 0 : -1) ? 1 : 0;
    if (dot)
    {
       finalize(0, S_TMP);
@@ -1180,94 +1156,45 @@ extern "C" int hda_amg_level0_sweep(hda_amg_t h, int dir, const double *b, const
 extern "C" int hda_amg_rebind(hda_amg_t h, hda_csr_t A)
 {
    HDA_TRY
-   HDA_REQUIRE(h && h->amg && A, "hda_amg_rebind: null argument");
-   h->amg->rebind(A->get(), nullptr);
+   HDA_REQUIRE(h && h->pc.amg && A, "hda_amg_rebind: null argument");
+   h->pc.amg->rebind(A->get(), nullptr);
    HDA_CATCH
 }
 extern "C" int hda_amg_level_cf(hda_amg_t h, int level, int *cf)
 {
    HDA_TRY
-   HDA_REQUIRE(level >= 0 && level < h->amg->num_levels() - 1, "level has no C/F splitting");
-   auto &L = h->amg->level(level);
+   HDA_REQUIRE(level >= 0 && level < h->pc.amg->num_levels() - 1, "level has no C/F splitting");
+   auto &L = h->pc.amg->level(level);
    L.cf.download(cf, L.cf.size());
    HDA_CATCH
 }
-extern "C" int hda_amg_blocks(hda_amg_t h) { return (h && h->amg) ? h->amg->blocks_used : 0; }
+extern "C" int hda_amg_blocks(hda_amg_t h) { return (h && h->pc.amg) ? h->pc.amg->blocks_used : 0; }
 extern "C" int hda_amg_level_blocks(hda_amg_t h, int level, int64_t *part)
 {
    HDA_TRY
-   HDA_REQUIRE(h && h->amg && level >= 0 && level < h->amg->num_levels(), "no such level");
-   const std::vector<int> &bp = h->amg->level_blocks(level);
-   if (bp.size() < 2) { part[0] = 0; part[1] = h->amg->level_A(level).nrows; }
+   HDA_REQUIRE(h && h->pc.amg && level >= 0 && level < h->pc.amg->num_levels(), "no such level");
+   const std::vector<int> &bp = h->pc.amg->level_blocks(level);
+   if (bp.size() < 2) { part[0] = 0; part[1] = h->pc.amg->level_A(level).nrows; }
    else for (size_t q = 0; q < bp.size(); q++) part[q] = bp[q];
    HDA_CATCH
 }
 extern "C" int hda_amg_complexities(hda_amg_t h, double *grid, double *op)
 {
    if (!h) return HDA_ERR_ARG;
-   if (grid) *grid = h->amg->grid_complexity();
-   if (op) *op = h->amg->operator_complexity();
+   if (grid) *grid = h->pc.amg->grid_complexity();
+   if (op) *op = h->pc.amg->operator_complexity();
    return HDA_OK;
 }
-extern "C" double hda_amg_vcycle_bytes(hda_amg_t h) { return h ? h->amg->vcycle_bytes() : 0.0; }
+extern "C" double hda_amg_vcycle_bytes(hda_amg_t h) { return h ? h->pc.amg->vcycle_bytes() : 0.0; }
 
 extern "C" int hda_amg_vcycle(hda_amg_t h, const double *b, double *x)
-{
+{ // one application of the preconditioner from a zero guess
    HDA_TRY
-   if (h->mgr)
-   { // one application of the MGR preconditioner from a zero guess
-      const DCsr    &m = h->A->get();
-      DArray<double> db, dx((size_t)std::max(std::max(m.ncols, m.nrows), 1));
-      db.upload(b, (size_t)m.nrows);
-      h->mgr->solve(db.data(), dx.data(), true);
-      dx.download(x, (size_t)m.nrows);
-      gs_free_check();
-      return HDA_OK;
-   }
-   if (h->ams)
-   { // one application of the AMS preconditioner from a zero guess
-      const DCsr    &m = h->A->get();
-      DArray<double> db, dx((size_t)std::max(std::max(m.ncols, m.nrows), 1));
-      db.upload(b, (size_t)m.nrows);
-      h->ams->apply(db.data(), dx.data());
-      dx.download(x, (size_t)m.nrows);
-      gs_free_check();
-      return HDA_OK;
-   }
-   if (h->fsai)
-   { // one application of the FSAI preconditioner from a zero guess
-      const DCsr    &m = h->A->get();
-      DArray<double> db, dx((size_t)std::max(std::max(m.ncols, m.nrows), 1));
-      db.upload(b, (size_t)m.nrows);
-      fsai_solve(*h->fsai, m, nullptr, db.data(), dx.data(), true, h->ilu_r, h->ilu_c);
-      dx.download(x, (size_t)m.nrows);
-      return HDA_OK;
-   }
-   if (h->schwarz)
-   { // one application of the Schwarz preconditioner from a zero guess
-      const DCsr    &m = h->A->get();
-      DArray<double> db, dx((size_t)std::max(std::max(m.ncols, m.nrows), 1));
-      db.upload(b, (size_t)m.nrows);
-      schwarz_solve(*h->schwarz, m, db.data(), dx.data(), true, h->ilu_r, h->ilu_c);
-      dx.download(x, (size_t)m.nrows);
-      gs_free_check();
-      return HDA_OK;
-   }
-   if (h->ilu)
-   { // one application of the ILU preconditioner from a zero guess
-      const DCsr    &m = h->A->get();
-      DArray<double> db, dx((size_t)std::max(std::max(m.ncols, m.nrows), 1));
-      db.upload(b, (size_t)m.nrows);
-      ilu_solve(*h->ilu, m, nullptr, db.data(), dx.data(), true, h->ilu_r, h->ilu_c);
-      dx.download(x, (size_t)m.nrows);
-      gs_free_check();
-      return HDA_OK;
-   }
-   const int      n = h->amg->level_A(0).nrows;
-   DArray<double> db, dx(std::max<size_t>(h->amg->vec_len0(), (size_t)std::max(h->amg->level_A(0).ncols, 1)));
-   db.upload(b, (size_t)n);
-   h->amg->apply(db.data(), dx.data(), -1);
-   dx.download(x, (size_t)n);
+   const DCsr    &m = h->pc.amg ? h->pc.amg->level_A(0) : h->A->get();
+   DArray<double> db, dx(std::max(h->pc.vec_len(m), (size_t)std::max(m.ncols, 1)));
+   db.upload(b, (size_t)m.nrows);
+   h->pc.solve(m, nullptr, db.data(), dx.data(), true);
+   dx.download(x, (size_t)m.nrows);
    gs_free_check();
    HDA_CATCH
 }
@@ -1286,34 +1213,9 @@ static int run_krylov(int kind, hda_csr_t A, hda_amg_t amg, const hda_krylov_par
    HDA_HIP(hipMemcpyAsync(dx.data(), x, sizeof(double) * (size_t)m.nrows, hipMemcpyHostToDevice, Context::get().stream));
    Context::get().sync();
    PrecondFn M;
-   if (amg && amg->mgr)
-      M = [amg, &m](const double *r, double *z, int slot) {
-         amg->mgr->solve(r, z, true);
-         if (slot >= 0) dot(m.nrows, r, z, slot);
-      };
-   else if (amg && amg->ams)
-      M = [amg, &m](const double *r, double *z, int slot) {
-         amg->ams->apply(r, z);
-         if (slot >= 0) dot(m.nrows, r, z, slot);
-      };
-   else if (amg && amg->fsai)
-      M = [amg, &m](const double *r, double *z, int slot) {
-         fsai_solve(*amg->fsai, m, nullptr, r, z, true, amg->ilu_r, amg->ilu_c);
-         if (slot >= 0) dot(m.nrows, r, z, slot);
-      };
-   else if (amg && amg->schwarz)
-      M = [amg, &m](const double *r, double *z, int slot) {
-         schwarz_solve(*amg->schwarz, m, r, z, true, amg->ilu_r, amg->ilu_c);
-         if (slot >= 0) dot(m.nrows, r, z, slot);
-      };
-   else if (amg && amg->ilu)
-      M = [amg, &m](const double *r, double *z, int slot) {
-         ilu_solve(*amg->ilu, m, nullptr, r, z, true, amg->ilu_r, amg->ilu_c);
-         if (slot >= 0) dot(m.nrows, r, z, slot);
-      };
-   else if (amg) M = [amg](const double *r, double *z, int slot) { amg->amg->apply_offering(r, z, slot); };
+   if (amg) M = amg->pc.as_fn(m, nullptr);
    KrylovParams  k   = to_kparams(kp);
-   LinOp         op(m, nullptr, (amg && amg->amg) ? amg->amg->vec_len0() : 0);
+   LinOp         op(m, nullptr, (amg && amg->pc.amg) ? amg->pc.amg->vec_len0() : 0);
    KrylovResult  res = kind == 1 ? gmres(op, M, k, db.data(), dx.data()) : kind == 2 ? fgmres(op, M, k, db.data(), dx.data())
                      : kind == 3 ? bicgstab(op, M, k, db.data(), dx.data()) : pcg(op, M, k, db.data(), dx.data());
    dx.download(x, (size_t)m.nrows);
@@ -1371,8 +1273,8 @@ extern "C" int hda_time_kernel(int kind, hda_csr_t A, hda_amg_t amg, int reps, d
          case 2: residual(m, x.data(), b.data(), y.data()); break;
          case 3:
             HDA_REQUIRE(amg, "V-cycle timing needs a hierarchy");
-            HDA_REQUIRE(nv >= amg->amg->vec_len0(), "vector too short for the hierarchy");
-            amg->amg->apply(b.data(), y.data(), -1);
+            HDA_REQUIRE(nv >= amg->pc.amg->vec_len0(), "vector too short for the hierarchy");
+            amg->pc.amg->apply(b.data(), y.data(), -1);
             break;
          default: throw Error("unknown kernel kind");
       }
@@ -1393,7 +1295,7 @@ extern "C" int hda_time_kernel(int kind, hda_csr_t A, hda_amg_t amg, int reps, d
    if (bytes)
    {
       const double sb = spmv_alg_bytes(m);
-      *bytes = (kind == 0) ? sb : (kind == 1) ? sb + 16.0 * m.nrows : (kind == 2) ? sb + 8.0 * m.nrows : amg->amg->vcycle_bytes();
+      *bytes = (kind == 0) ? sb : (kind == 1) ? sb + 16.0 * m.nrows : (kind == 2) ? sb + 8.0 * m.nrows : amg->pc.amg->vcycle_bytes();
    }
    HDA_CATCH
 }
@@ -1410,7 +1312,7 @@ extern "C" int hda_solve_device(hda_csr_t A, hda_amg_t amg, const hda_krylov_par
    Context       &ctx = Context::get();
    const DCsr    &m   = A->get();
    const int      n   = m.nrows;
-   DArray<double> b, x(std::max<size_t>((size_t)std::max(m.ncols, 1), amg && amg->amg ? amg->amg->vec_len0() : 0)), r((size_t)std::max(n, 1));
+   DArray<double> b, x(std::max<size_t>((size_t)std::max(m.ncols, 1), amg && amg->pc.amg ? amg->pc.amg->vec_len0() : 0)), r((size_t)std::max(n, 1));
    if (b_host) b.upload(b_host, (size_t)n);
    else if (A->rhs_ref)
    {
@@ -1433,10 +1335,10 @@ extern "C" int hda_solve_device(hda_csr_t A, hda_amg_t amg, const hda_krylov_par
    finalize(0, S_TMP);
    const double bn = std::sqrt(read_scalar(S_TMP));
    PrecondFn M;
-   if (amg) M = [amg](const double *rr, double *zz, int slot) { amg->amg->apply_offering(rr, zz, slot); };
+   if (amg) M = [amg](const double *rr, double *zz, int slot) { amg->pc.amg->apply_offering(rr, zz, slot); };
    KrylovParams k = to_kparams(kp);
    k.profile_k1   = (k1_avg_ms != nullptr);
-   LinOp op(m, multi ? A->halo : nullptr, amg ? amg->amg->vec_len0() : 0);
+   LinOp op(m, multi ? A->halo : nullptr, amg ? amg->pc.amg->vec_len0() : 0);
    KrylovResult res;
    double       k1_sum = 0.0;
    long         k1_cnt = 0;
@@ -1473,7 +1375,7 @@ extern "C" int hda_format_bytes(hda_csr_t A, hda_amg_t amg, double *pcg_iteratio
    HDA_TRY
    const DCsr &m = A->get();
    if (pcg_iteration) *pcg_iteration = pcg_iteration_bytes(m, true);
-   if (vcycle) *vcycle = amg ? amg->amg->vcycle_bytes(true) : 0.0;
+   if (vcycle) *vcycle = amg ? amg->pc.amg->vcycle_bytes(true) : 0.0;
    if (spmv) *spmv = matrix_stream_bytes(m, true) + rowptr_stream_bytes(m, true) + 8.0 * m.ncols + 8.0 * m.nrows;
    // storage form the products of A use: 0 plain CSR, 1 entry-coded stencil operator, 2 row-class coded, 3 windowed CSR,
    // 4 value-coded, 5 value-coded + windowed
@@ -1558,7 +1460,8 @@ extern "C" int hda_borrow_hypredrv(void *hypredrv, hda_csr_t *A, hda_amg_t *amg)
    {
       HDA_REQUIRE(g, "hda_borrow_hypredrv: the preconditioner is not a set-up BoomerAMG hierarchy");
       auto h = std::make_unique<hda_amg_s>();
-      h->amg = g;
+      h->pc.amg  = g;
+      h->pc.kind = Precond::AMG;
       *amg   = h.release();
    }
    HDA_CATCH

@@ -485,20 +485,4 @@ double Fsai::apply_bytes() const
    return 2.0 * (12.0 * G.nnz + 4.0 * (n + 1.0)) + 4.0 * 8.0 * n;
 }
 
-// max_iter iterations x += omega G^T G (b - A x); from a zero guess the first one skips the product
-void fsai_solve(Fsai &F, const DCsr &A, const HaloPlan *halo, const double *b, double *x, bool zero_guess, DArray<double> &r, DArray<double> &c, int iters)
-{
-   const int n = A.nrows;
-   if (r.size() < (size_t)std::max(n, 1)) r.alloc((size_t)std::max(n, 1));
-   if (c.size() < (size_t)std::max(n, 1)) c.alloc((size_t)std::max(n, 1));
-   const int its = iters > 0 ? iters : std::max(F.prm.max_iter, 1);
-   for (int it = 0; it < its; it++)
-   {
-      if (zero_guess && it == 0) { F.apply(b, x); continue; } // b - A*0 = b exactly
-      residual(A, x, b, r.data(), halo);
-      F.apply(r.data(), c.data());
-      axpy(n, 1.0, c.data(), x);
-   }
-}
-
 } // namespace hda

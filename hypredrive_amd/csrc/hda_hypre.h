@@ -2,7 +2,7 @@
 #pragma once
 
 #include "../../include/HYPRE.h"
-#include "hda_krylov.h"
+#include "hda_precond.h"
 
 #include <memory>
 #include <string>
@@ -89,30 +89,25 @@ struct hypre_Solver_struct {
                              restriction = 0, relax_order = 0, sabs = 0, seq_threshold = 0, relax_type_all = -1, filter_functions = 0;
    HYPRE_PtrToSolverFcn      precond = nullptr, precond_setup = nullptr;
    HYPRE_Solver              precond_solver = nullptr;
-   std::unique_ptr<hda::Amg> amg;
+   hda::Precond              pc; // what Setup built: the object of this handle's kind, with the work vectors of its solves
    // HYPRE_BoomerAMGSetGridRelaxPoints: a copy of the schedule (down, up, coarse; one entry per sweep as the sweep counts were when it
    // was set), checked at Setup
    bool                      grid_points_set = false;
    std::vector<int>          grid_points[3];
    // HYPRE_ILU* handle, and the ILU arguments of BoomerAMG's complex smoother (HYPRE_BoomerAMGSetILU*)
-   std::unique_ptr<hda::Ilu> ilu;
    hda::IluParams            ilup;
    int                       ilu_type = 0, ilu_fill = 0, ilu_reordering = 0; // checked at Setup: bj-iluk / 0 / 0 only
-   hda::DArray<double>       ilu_r, ilu_c;
    // HYPRE_Schwarz* handle: what the setters recorded (hypre's numbering: variant 10 ras-iluk, 11 as-iluk, ...), checked at Setup
-   std::unique_ptr<hda::Schwarz> schwarz;
    int                           sw_variant = 0, sw_overlap = 1, sw_domain_type = 2, sw_num_functions = 1, sw_nonsymm = 0, sw_local_solver = 0,
                                  sw_fill = 0, sw_max_iter = 1, sw_print_level = 0, sw_logging = 0;
    double                        sw_weight = 1.0, sw_tol = 0.0;
    // HYPRE_FSAI* handle, and the FSAI arguments of BoomerAMG's complex smoother (HYPRE_BoomerAMGSetFSAI*): what the setters recorded
    // (defaults: the reference's, src/internal/fsai.c:15-27 -- algo_type 1, the adaptive bj-afsai), checked at Setup
-   std::unique_ptr<hda::Fsai>    fsai;
    hda::FsaiParams               fsaip;
    int                           fs_algo = 1, fs_ls_type = 1, fs_max_steps = 5, fs_max_step_size = 3, fs_print_level = 0;
    double                        fs_kap_tol = 1.0e-3, fs_tol = 0.0;
    // HYPRE_AMS* handle: what the setters recorded (defaults: the reference's GPU build, src/internal/ams.c:15-22), checked at Setup; G and
    // the coordinate vectors are borrowed, as in hypre
-   std::unique_ptr<hda::Ams>     ams;
    hda::AmsParams                amsp;
    hda::AmsAmgOptions            ams_alpha, ams_beta;
    int                           ams_print_level = 0, ams_proj_freq = 5; // (proj_freq and omega act in the singular case / with relax_type 2 only)
@@ -120,7 +115,6 @@ struct hypre_Solver_struct {
    HYPRE_ParCSRMatrix            ams_G = nullptr;
    HYPRE_ParVector               ams_xyz[3] = {nullptr, nullptr, nullptr};
    // HYPRE_MGR* handle: what the setters recorded (hypre's per-level arrays, copied), built at Setup
-   std::unique_ptr<hda::Mgr>     mgr;
    int                           mgr_block_size = 0, mgr_levels = 0, mgr_max_iter = 1, mgr_cycle = 1, mgr_frelax_cycle = 1, mgr_gsmooth_cycle = 1;
    double                        mgr_coarse_th = 0.0;
    int                           mgr_nonglk_max_elmts = 1; // HYPRE_MGRSetNonGalerkinMaxElmts (hypre's default 1)

@@ -44,6 +44,9 @@ static bool have_device()
 }
 #define HY_NEED_DEVICE \
    if (!have_device()) return hypre_set_error(HYPRE_ERROR_GENERIC, "no HIP device visible: the MI355X solve path has no CPU fallback")
+// HDA_BLOCKS = V row blocks on one GPU (0: the setup's own choice); unset: dflt
+static int  env_blocks(int dflt) { const char *e = getenv("HDA_BLOCKS"); return e ? std::max(atoi(e), 0) : dflt; }
+static bool quiet() { return getenv("HDA_QUIET") != nullptr; } // HDA_QUIET: no notes about row blocks on stderr
 
 // ------------------------------------------------------------------ utilities
 
@@ -1089,17 +1092,6 @@ extern "C" HYPRE_Int HYPRE_ParCSRGMRESSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A
 extern "C" HYPRE_Int HYPRE_ParCSRFlexGMRESSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x) { return krylov_setup(s, A, b, x); }
 extern "C" HYPRE_Int HYPRE_ParCSRBiCGSTABSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x) { return krylov_setup(s, A, b, x); }
 
-// length Krylov work vectors need so that a BoomerAMG preconditioner can use them as level-0
-// vectors directly (any other callback only sees the owned part)
-static size_t precond_veclen(HYPRE_Solver s)
-{
-   HYPRE_Solver p = s->precond_solver;
-   // hypredrive hands a cookie, not the AMG handle (src/internal/solver.c:538): the cookie
-   // type registers its vector length through hda_register_precond_veclen below
-   (void)p;
-   return 0;
-}
-
 namespace hda {
 static std::unordered_set<const void *> &live_solvers()
 {
@@ -1125,9 +1117,9 @@ static HYPRE_Int krylov_solve(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVec
    set_stage("Krylov solve");
    HDA_REQUIRE(A && A->assembled, "Krylov solve needs an assembled matrix");
    x->ensure_device();
-   size_t veclen = std::max(g_precond_veclen, precond_veclen(s));
-   if (is_live_solver(s->precond_solver) && s->precond_solver->kind == HDA_SOLVER_AMG && s->precond_solver->amg)
-      veclen = std::max(veclen, s->precond_solver->amg->vec_len0());
+   size_t veclen = g_precond_veclen;
+   if (is_live_solver(s->precond_solver) && s->precond_solver->kind == HDA_SOLVER_AMG && s->precond_solver->pc.amg)
+      veclen = std::max(veclen, s->precond_solver->pc.amg->vec_len0());
    LinOp     op(A->A, Comm::world().size > 1 ? &A->halo : nullptr, veclen);
    PrecondFn M;
    if (s->precond)
@@ -1392,12 +1384,14 @@ extern "C" HYPRE_Int HYPRE_BoomerAMGSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, 
    s->ap.num_functions = std::max(s->num_functions, 1);
    // row blocks (the reference's hybrid Gauss-Seidel / HMIS at np = V on one GPU): HDA_BLOCKS = V, 1 = the sequential algorithms,
    // unset = the setup's own choice (one block up to HDA_BLOCKS_MIN_ROWS rows); across ranks the rank blocks are the blocks
-   s->ap.blocks = (Comm::world().size > 1) ? 1 : (getenv("HDA_BLOCKS") ? std::max(atoi(getenv("HDA_BLOCKS")), 0) : 0);
-   s->amg       = std::make_unique<Amg>(s->ap);
+   s->ap.blocks = (Comm::world().size > 1) ? 1 : env_blocks(0);
+   s->pc.owned_amg = std::make_unique<Amg>(s->ap);
+   s->pc.amg       = s->pc.owned_amg.get();
+   s->pc.kind      = Precond::AMG;
    if (s->ap.num_functions > 1)
    {
-      if (s->dof_func_ptr) s->amg->dof_func0.assign(s->dof_func_ptr, s->dof_func_ptr + A->nloc);
-      s->amg->dof_row_offset = A->ilower; // hypre's default: (global row) mod num_functions
+      if (s->dof_func_ptr) s->pc.amg->dof_func0.assign(s->dof_func_ptr, s->dof_func_ptr + A->nloc);
+      s->pc.amg->dof_row_offset = A->ilower; // hypre's default: (global row) mod num_functions
    }
    if (Comm::world().size > 1)
    {
@@ -1413,20 +1407,49 @@ extern "C" HYPRE_Int HYPRE_BoomerAMGSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, 
       //  options beside the path, one-rank kernels; so are extended (14), mm-ext (16), one-point (100) and multipass (4))
       if ((mode && !strcmp(mode, "replicated")) || s->ap.coarsen_type != 8 || s->ap.num_functions > 1 || s->ap.smooth_num_levels > 1 || s->ap.agg_num_levels > 0 ||
           s->ap.interp_type != 6 || s->ap.restrict_type != 0 || !s->ap.points_down.empty() || !s->ap.points_up.empty())
-         s->amg->setup_dist(A->A, A->halo, A->part, A->ghost_gids);
-      else s->amg->setup_dist_partitioned(A->A, A->halo, A->part, A->ghost_gids);
+         s->pc.amg->setup_dist(A->A, A->halo, A->part, A->ghost_gids);
+      else s->pc.amg->setup_dist_partitioned(A->A, A->halo, A->part, A->ghost_gids);
    }
-   else s->amg->setup(A->A);
-   hda_register_precond_veclen(s->amg->vec_len0());
+   else s->pc.amg->setup(A->A);
+   hda_register_precond_veclen(s->pc.amg->vec_len0());
    if (s->ap.print_level > 0 && Comm::world().rank == 0)
    {
-      printf("\n BoomerAMG (MI355X): %d levels, grid complexity %.6f, operator complexity %.6f\n", s->amg->num_levels(),
-             s->amg->grid_complexity(), s->amg->operator_complexity());
+      printf("\n BoomerAMG (MI355X): %d levels, grid complexity %.6f, operator complexity %.6f\n", s->pc.amg->num_levels(),
+             s->pc.amg->grid_complexity(), s->pc.amg->operator_complexity());
       printf(" coarsening %s (%d)\n", amg_coarsen_name(s->ap.coarsen_type) ? amg_coarsen_name(s->ap.coarsen_type) : "?", s->ap.coarsen_type);
-      if (s->amg->blocks_used > 1)
-         printf(" %d row blocks (hybrid Gauss-Seidel / HMIS / RS / Falgout as on %d ranks)\n", s->amg->blocks_used, s->amg->blocks_used);
+      if (s->pc.amg->blocks_used > 1)
+         printf(" %d row blocks (hybrid Gauss-Seidel / HMIS / RS / Falgout as on %d ranks)\n", s->pc.amg->blocks_used, s->pc.amg->blocks_used);
       printf("\n");
    }
+   HY_CATCH
+}
+
+// body(xp) on the iterate of x with room for `need` entries: x's own buffer when it is that long, otherwise a temporary with the owned
+// part copied in before and out after (a caller's vector holds its owned entries; level-0 vectors of a row block carry ghosts behind them)
+template <class Body>
+static void with_room(HYPRE_ParVector x, int nloc, size_t need, Body body)
+{
+   if (x->capacity >= need) { body(x->data()); return; }
+   DArray<double> xe(need);
+   copy(nloc, x->data(), xe.data());
+   body(xe.data());
+   copy(nloc, xe.data(), x->data());
+}
+// HYPRE_{ILU,Schwarz,FSAI,AMS,MGR}Solve: the kind's own checks of the handle (and MGR's rebind), then its solve from the guess the Krylov
+// loop's hint names.  stage: the iterate gets room for the kind's level-0 vectors (the kinds that run on row partitions)
+template <class Check>
+static HYPRE_Int precond_solve(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x, bool stage, Check check)
+{
+   HY_NEED_DEVICE;
+   HY_TRY
+   check();
+   x->ensure_device();
+   const bool      zero = precond_hints().zero_guess;
+   const HaloPlan *halo = Comm::world().size > 1 ? &A->halo : nullptr;
+   auto            body = [&](double *xp) { s->pc.solve(A->A, halo, b->data(), xp, zero); };
+   if (stage) with_room(x, A->nloc, s->pc.vec_len(A->A), body);
+   else body(x->data());
+   s->amg_iters = s->pc.iterations();
    HY_CATCH
 }
 
@@ -1434,61 +1457,53 @@ extern "C" HYPRE_Int HYPRE_BoomerAMGSolve(HYPRE_Solver s, HYPRE_ParCSRMatrix A, 
 {
    HY_NEED_DEVICE;
    HY_TRY
-   HDA_REQUIRE(s && s->amg, "BoomerAMGSolve before BoomerAMGSetup");
-   if (!s->amg->bound_to(A->A)) s->amg->rebind(A->A, Comm::world().size > 1 ? &A->halo : nullptr); // reused hierarchy, later system
+   HDA_REQUIRE(s && s->pc.amg, "BoomerAMGSolve before BoomerAMGSetup");
+   if (!s->pc.amg->bound_to(A->A)) s->pc.amg->rebind(A->A, Comm::world().size > 1 ? &A->halo : nullptr); // reused hierarchy, later system
    x->ensure_device();
-   PrecondHints  &h   = precond_hints();
-   const size_t   need = s->amg->vec_len0();
-   double        *xp  = x->data();
-   DArray<double> xe;
-   const bool     staged = x->capacity < need;
-   if (staged)
-   {
-      xe.alloc(need);
-      copy(A->nloc, x->data(), xe.data());
-      xp = xe.data();
-   }
-   if (h.zero_guess && s->ap.max_iter == 1)
-   {
-      s->amg->apply_offering(b->data(), xp, h.dot_slot); // (honours and renews the first-sweep offer of PCG)
-      if (h.dot_slot >= 0) h.dot_done = true;
-      s->amg_iters = 1;
-   }
-   else
-   {
-      // stand-alone solver use: up to max_iter cycles, optional relative residual test
-      double bn = 0.0;
-      DArray<double> r, xs;
-      if (s->ap.tol > 0.0)
+   PrecondHints &h    = precond_hints();
+   const size_t  need = s->pc.amg->vec_len0();
+   with_room(x, A->nloc, need, [&](double *xp) {
+      if (h.zero_guess && s->ap.max_iter == 1)
       {
-         dot(A->nloc, b->data(), b->data(), 0);
-         finalize(0, S_TMP);
-         bn = std::sqrt(read_scalar(S_TMP));
-         r.alloc((size_t)std::max(A->nloc, 1));
-         xs.alloc(std::max(need, (size_t)A->A.ncols));
+         s->pc.amg->apply_offering(b->data(), xp, h.dot_slot); // (honours and renews the first-sweep offer of PCG)
+         if (h.dot_slot >= 0) h.dot_done = true;
+         s->amg_iters = 1;
       }
-      AmgParams one = s->amg->prm;
-      s->amg_iters  = 0;
-      for (int it = 0; it < std::max(s->ap.max_iter, 1); it++)
+      else
       {
-         s->amg->prm.max_iter = 1;
-         s->amg->solve(b->data(), xp);
-         s->amg_iters++;
+         // stand-alone solver use: up to max_iter cycles, optional relative residual test
+         double bn = 0.0;
+         DArray<double> r, xs;
          if (s->ap.tol > 0.0)
          {
-            copy(A->nloc, xp, xs.data());
-            halo_exchange(A->halo, xs.data());
-            residual(A->A, xs.data(), b->data(), r.data());
-            dot(A->nloc, r.data(), r.data(), 0);
+            dot(A->nloc, b->data(), b->data(), 0);
             finalize(0, S_TMP);
-            s->amg_rel = std::sqrt(read_scalar(S_TMP)) / (bn > 0.0 ? bn : 1.0);
-            if (s->amg_rel <= s->ap.tol) break;
+            bn = std::sqrt(read_scalar(S_TMP));
+            r.alloc((size_t)std::max(A->nloc, 1));
+            xs.alloc(std::max(need, (size_t)A->A.ncols));
          }
+         AmgParams one = s->pc.amg->prm;
+         s->amg_iters  = 0;
+         for (int it = 0; it < std::max(s->ap.max_iter, 1); it++)
+         {
+            s->pc.amg->prm.max_iter = 1;
+            s->pc.amg->solve(b->data(), xp);
+            s->amg_iters++;
+            if (s->ap.tol > 0.0)
+            {
+               copy(A->nloc, xp, xs.data());
+               halo_exchange(A->halo, xs.data());
+               residual(A->A, xs.data(), b->data(), r.data());
+               dot(A->nloc, r.data(), r.data(), 0);
+               finalize(0, S_TMP);
+               s->amg_rel = std::sqrt(read_scalar(S_TMP)) / (bn > 0.0 ? bn : 1.0);
+               if (s->amg_rel <= s->ap.tol) break;
+            }
+         }
+         s->pc.amg->prm = one;
+         if (s->ap.tol > 0.0) gs_free_check(); // (stand-alone solver with a residual test: the host is in step anyway -- report an aborted block sweep here)
       }
-      s->amg->prm = one;
-      if (s->ap.tol > 0.0) gs_free_check(); // (stand-alone solver with a residual test: the host is in step anyway -- report an aborted block sweep here)
-   }
-   if (staged) copy(A->nloc, xp, x->data());
+   });
    HY_CATCH
 }
 // ------------------------------------------------------------------------ ILU
@@ -1527,41 +1542,23 @@ extern "C" HYPRE_Int HYPRE_ILUSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_
    HDA_REQUIRE(s->ilu_type == 0, "ILU: only type bj-iluk (0) is implemented on MI355X; ilut / gmres- / nsh- / ras- / ddpq- variants are not");
    HDA_REQUIRE(s->ilu_fill == 0, "ILU: only fill_level 0 is implemented");
    HDA_REQUIRE(s->ilu_reordering == 0, "ILU: only reordering 0 (natural order) is implemented");
-   s->ilu = std::make_unique<Ilu>();
+   s->pc.kind = Precond::ILU;
+   s->pc.ilu  = std::make_unique<Ilu>();
    // `preconditioner: ilu` factors the WHOLE matrix of a rank, as the reference does at np = 1 (round-4 ADVICE: the automatic row
    // blocks made it block-Jacobi ILU silently, dropping every coupling between blocks).  Row blocks (bj-iluk at np = V on one GPU;
    // the exact substitutions then run as block sweeps) are opt-in: HDA_BLOCKS = V, 0 = the setup's own choice; always said.
-   s->ilup.blocks = (Comm::world().size > 1 || !s->ilup.tri_solve) ? 1 : (getenv("HDA_BLOCKS") ? std::max(atoi(getenv("HDA_BLOCKS")), 0) : 1);
-   s->ilu->setup(A->A, s->ilup);
-   if (Comm::world().rank == 0 && s->ilu->blocks_used() > 1 && !getenv("HDA_QUIET"))
+   s->ilup.blocks = (Comm::world().size > 1 || !s->ilup.tri_solve) ? 1 : env_blocks(1);
+   s->pc.ilu->setup(A->A, s->ilup);
+   if (Comm::world().rank == 0 && s->pc.ilu->blocks_used() > 1 && !quiet())
       fprintf(stderr, "[hypredrv_amd] ILU(0): %d row blocks (HDA_BLOCKS): block-Jacobi ILU as the reference computes it on %d ranks; couplings between blocks are dropped\n",
-              s->ilu->blocks_used(), s->ilu->blocks_used());
+              s->pc.ilu->blocks_used(), s->pc.ilu->blocks_used());
    hda_register_precond_veclen((size_t)std::max(A->A.ncols, A->A.nrows));
    HY_CATCH
 }
 
 extern "C" HYPRE_Int HYPRE_ILUSolve(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
 {
-   HY_NEED_DEVICE;
-   HY_TRY
-   HDA_REQUIRE(s && s->ilu, "ILUSolve before ILUSetup");
-   x->ensure_device();
-   PrecondHints  &h    = precond_hints();
-   const bool     multi = Comm::world().size > 1;
-   const size_t   need = (size_t)std::max(A->A.ncols, A->A.nrows);
-   double        *xp   = x->data();
-   DArray<double> xe;
-   const bool     staged = x->capacity < need;
-   if (staged)
-   {
-      xe.alloc(need);
-      copy(A->nloc, x->data(), xe.data());
-      xp = xe.data();
-   }
-   ilu_solve(*s->ilu, A->A, multi ? &A->halo : nullptr, b->data(), xp, h.zero_guess, s->ilu_r, s->ilu_c);
-   s->amg_iters = std::max(s->ilup.max_iter, 1);
-   if (staged) copy(A->nloc, xp, x->data());
-   HY_CATCH
+   return precond_solve(s, A, b, x, true, [&] { HDA_REQUIRE(s && s->pc.ilu, "ILUSolve before ILUSetup"); });
 }
 HY_GETTER(HYPRE_ILUGetNumIterations, HYPRE_Int, s->amg_iters)
 HY_GETTER(HYPRE_ILUGetFinalRelativeResidualNorm, HYPRE_Real, s->amg_rel)
@@ -1642,11 +1639,12 @@ extern "C" HYPRE_Int HYPRE_SchwarzSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HY
    SchwarzParams p;
    p.variant = s->sw_variant - 10; p.overlap = s->sw_overlap; p.fill = s->sw_fill; p.max_iter = s->sw_max_iter; p.weight = s->sw_weight;
    // one subdomain per rank is hypre's picture; on one GPU the row blocks play the ranks (HDA_BLOCKS = V, 0 = the setup's choice), as for ILU
-   p.blocks  = getenv("HDA_BLOCKS") ? std::max(atoi(getenv("HDA_BLOCKS")), 0) : 1;
-   s->schwarz = std::make_unique<Schwarz>();
-   s->schwarz->setup(A->A, p);
-   const Schwarz &S = *s->schwarz;
-   if (S.V > 1 && !getenv("HDA_QUIET"))
+   p.blocks  = env_blocks(1);
+   s->pc.kind    = Precond::SCHWARZ;
+   s->pc.schwarz = std::make_unique<Schwarz>();
+   s->pc.schwarz->setup(A->A, p);
+   const Schwarz &S = *s->pc.schwarz;
+   if (S.V > 1 && !quiet())
       fprintf(stderr, "[hypredrv_amd] Schwarz: %d row blocks (HDA_BLOCKS): one subdomain per block, as the reference has one per rank on %d ranks\n", S.V, S.V);
    if (s->sw_print_level >= 1)
       printf("Schwarz (%s): %d subdomains, overlap %d, N_ext / n = %.3f, ILU(%d), nnz(LU) / nnz(A) = %.3f\n", s->sw_variant == 10 ? "ras-iluk" : "as-iluk",
@@ -1657,14 +1655,7 @@ extern "C" HYPRE_Int HYPRE_SchwarzSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HY
 
 extern "C" HYPRE_Int HYPRE_SchwarzSolve(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
 {
-   HY_NEED_DEVICE;
-   HY_TRY
-   HDA_REQUIRE(s && s->schwarz, "SchwarzSolve before SchwarzSetup");
-   x->ensure_device();
-   PrecondHints &h = precond_hints();
-   schwarz_solve(*s->schwarz, A->A, b->data(), x->data(), h.zero_guess, s->ilu_r, s->ilu_c);
-   s->amg_iters = std::max(s->sw_max_iter, 1);
-   HY_CATCH
+   return precond_solve(s, A, b, x, false, [&] { HDA_REQUIRE(s && s->pc.schwarz, "SchwarzSolve before SchwarzSetup"); });
 }
 
 // ------------------------------------------------------------------------ FSAI
@@ -1738,11 +1729,12 @@ extern "C" HYPRE_Int HYPRE_FSAISetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE
    HDA_REQUIRE(A && A->assembled, "FSAISetup needs an assembled matrix");
    FsaiParams p = s->fsaip;
    // "bj": block Jacobi over the ranks in hypre; on one GPU the row blocks play the ranks (HDA_BLOCKS = V, 0 = the setup's choice), as for ILU
-   p.blocks = getenv("HDA_BLOCKS") ? std::max(atoi(getenv("HDA_BLOCKS")), 0) : 1;
-   s->fsai  = std::make_unique<Fsai>();
-   s->fsai->setup(A->A, p);
-   const Fsai &F = *s->fsai;
-   if (F.nblocks > 1 && !getenv("HDA_QUIET"))
+   p.blocks = env_blocks(1);
+   s->pc.kind = Precond::FSAI;
+   s->pc.fsai = std::make_unique<Fsai>();
+   s->pc.fsai->setup(A->A, p);
+   const Fsai &F = *s->pc.fsai;
+   if (F.nblocks > 1 && !quiet())
       fprintf(stderr, "[hypredrv_amd] FSAI: %d row blocks (HDA_BLOCKS): no pattern leaves its block, as on %d ranks of the reference\n", F.nblocks, F.nblocks);
    if (s->fs_print_level >= 1)
       printf("FSAI (bj-sfsai): num_levels %d, threshold %g, max_nnz_row %d, nnz(G) / n = %.3f, omega = %.6f (%d power steps), fallback rows %d\n", p.num_levels,
@@ -1753,14 +1745,7 @@ extern "C" HYPRE_Int HYPRE_FSAISetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE
 
 extern "C" HYPRE_Int HYPRE_FSAISolve(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
 {
-   HY_NEED_DEVICE;
-   HY_TRY
-   HDA_REQUIRE(s && s->fsai, "FSAISolve before FSAISetup");
-   x->ensure_device();
-   PrecondHints &h = precond_hints();
-   fsai_solve(*s->fsai, A->A, nullptr, b->data(), x->data(), h.zero_guess, s->ilu_r, s->ilu_c);
-   s->amg_iters = std::max(s->fsaip.max_iter, 1);
-   HY_CATCH
+   return precond_solve(s, A, b, x, false, [&] { HDA_REQUIRE(s && s->pc.fsai, "FSAISolve before FSAISetup"); });
 }
 
 // ------------------------------------------------------------------------ AMS
@@ -1855,9 +1840,10 @@ extern "C" HYPRE_Int HYPRE_AMSSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_
       v->ensure_device();
       c[k] = v->data();
    }
-   s->ams = std::make_unique<Ams>();
-   s->ams->setup(A->A, G->A, c, p);
-   Ams &S = *s->ams;
+   s->pc.kind = Precond::AMS;
+   s->pc.ams  = std::make_unique<Ams>();
+   s->pc.ams->setup(A->A, G->A, c, p);
+   Ams &S = *s->pc.ams;
    if (s->ams_print_level >= 1)
       printf("AMS (cycle %d, dimension %d): n_e %d, n_v %d, nnz(Pi) %d, A_G %d rows / %d levels, A_Pi %d rows / %d levels, repaired rows %d + %d\n",
              p.cycle_type, p.dimension, S.n_e, S.n_v, S.pi().nnz, S.a_g().nrows, S.b_g().num_levels(), S.a_pi().nrows, S.b_pi().num_levels(),
@@ -1867,28 +1853,13 @@ extern "C" HYPRE_Int HYPRE_AMSSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_
 }
 
 extern "C" HYPRE_Int HYPRE_AMSSolve(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
-{
-   HY_NEED_DEVICE;
-   HY_TRY
-   HDA_REQUIRE(s && is_live_solver(s) && s->kind == HDA_SOLVER_AMS, "AMSSolve: not an AMS handle");
-   HDA_REQUIRE(s->ams, "AMSSolve before AMSSetup");
-   HDA_REQUIRE(A && A->assembled && b && x, "AMSSolve needs an assembled matrix and two vectors");
-   HDA_REQUIRE(A->A.nrows == s->ams->n_e && b->nloc == A->A.nrows && x->nloc == A->A.nrows, "AMSSolve: the system is not the size of the one set up");
-   x->ensure_device();
-   const int     n = A->A.nrows;
-   PrecondHints &h = precond_hints();
-   if (h.zero_guess) s->ams->apply(b->data(), x->data());
-   else
-   { // the cycle is a stationary iteration: from x it gives x + M (b - A x)
-      const size_t len = (size_t)std::max(std::max(A->A.ncols, n), 1);
-      if (s->ilu_r.size() < len) s->ilu_r.alloc(len);
-      if (s->ilu_c.size() < len) s->ilu_c.alloc(len);
-      residual(A->A, x->data(), b->data(), s->ilu_r.data());
-      s->ams->apply(s->ilu_r.data(), s->ilu_c.data());
-      axpy(n, 1.0, s->ilu_c.data(), x->data());
-   }
-   s->amg_iters = std::max(s->amsp.max_iter, 1);
-   HY_CATCH
+{ // (the cycle is a stationary iteration: from x it gives x + M (b - A x))
+   return precond_solve(s, A, b, x, false, [&] {
+      HDA_REQUIRE(s && is_live_solver(s) && s->kind == HDA_SOLVER_AMS, "AMSSolve: not an AMS handle");
+      HDA_REQUIRE(s->pc.ams, "AMSSolve before AMSSetup");
+      HDA_REQUIRE(A && A->assembled && b && x, "AMSSolve needs an assembled matrix and two vectors");
+      HDA_REQUIRE(A->A.nrows == s->pc.ams->n_e && b->nloc == A->A.nrows && x->nloc == A->A.nrows, "AMSSolve: the system is not the size of the one set up");
+   });
 }
 
 // ------------------------------------------------------------------------ MGR
@@ -2078,7 +2049,7 @@ extern "C" HYPRE_Int HYPRE_MGRSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_
       if (q.grelax_sweeps <= 0) q.grelax_type = -1; // hypre: no global smoothing without sweeps
       // row blocks of a hybrid Gauss-Seidel global relaxation, as for BoomerAMG's sweeps: HDA_BLOCKS = V, 1 = one block (np = 1), unset = the
       // setup's choice (one block up to 100 000 rows; announced); across ranks the rank blocks are the blocks
-      q.grelax_blocks = (Comm::world().size > 1) ? 1 : (getenv("HDA_BLOCKS") ? std::max(atoi(getenv("HDA_BLOCKS")), 0) : 0);
+      q.grelax_blocks = (Comm::world().size > 1) ? 1 : env_blocks(0);
       if ((size_t)l < s->mgr_gsolver.size() && s->mgr_gsolver[(size_t)l])
       { // a smoother object handed over with HYPRE_MGRSetGlobalSmootherAtLevel (mgr.c: ILU with its own arguments)
          HYPRE_Solver gs = s->mgr_gsolver[(size_t)l];
@@ -2091,17 +2062,18 @@ extern "C" HYPRE_Int HYPRE_MGRSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_
       p.levels.push_back(q);
       prev = c;
    }
-   s->mgr = std::make_unique<Mgr>(p);
-   if (Comm::world().size > 1) s->mgr->setup_dist(A->A, A->halo, A->part, A->ghost_gids, labels);
-   else s->mgr->setup(A->A, labels);
-   hda_register_precond_veclen(s->mgr->vec_len0());
+   s->pc.kind = Precond::MGR;
+   s->pc.mgr  = std::make_unique<Mgr>(p);
+   if (Comm::world().size > 1) s->pc.mgr->setup_dist(A->A, A->halo, A->part, A->ghost_gids, labels);
+   else s->pc.mgr->setup(A->A, labels);
+   hda_register_precond_veclen(s->pc.mgr->vec_len0());
    if (s->ap.print_level > 0)
    { // the reduction hierarchy (global sizes), in the spirit of hypre's MGR setup printout
-      const int nl = s->mgr->num_reduction_levels();
+      const int nl = s->pc.mgr->num_reduction_levels();
       std::vector<long long> sz((size_t)(2 * (nl + 1)));
       for (int l = 0; l <= nl; l++)
       {
-         const DCsr &M        = s->mgr->matrix(l, 0);
+         const DCsr &M        = s->pc.mgr->matrix(l, 0);
          sz[(size_t)(2 * l)]     = M.nrows;
          sz[(size_t)(2 * l + 1)] = M.nnz;
       }
@@ -2125,38 +2097,22 @@ extern "C" HYPRE_Int HYPRE_MGRSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_
 
 extern "C" HYPRE_Int HYPRE_MGRSolve(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
 {
-   HY_NEED_DEVICE;
-   HY_TRY
-   HDA_REQUIRE(s && s->mgr, "MGRSolve before MGRSetup");
-   if (!s->mgr->bound_to(A->A)) s->mgr->rebind(A->A, Comm::world().size > 1 ? &A->halo : nullptr); // reused preconditioner, later system
-   x->ensure_device();
-   PrecondHints  &h    = precond_hints();
-   const size_t   need = s->mgr->vec_len0();
-   double        *xp   = x->data();
-   DArray<double> xe;
-   const bool     staged = x->capacity < need;
-   if (staged)
-   {
-      xe.alloc(need);
-      copy(A->nloc, x->data(), xe.data());
-      xp = xe.data();
-   }
-   s->mgr->solve(b->data(), xp, h.zero_guess);
-   s->amg_iters = std::max(s->mgr_max_iter, 1);
-   if (staged) copy(A->nloc, xp, x->data());
-   HY_CATCH
+   return precond_solve(s, A, b, x, true, [&] {
+      HDA_REQUIRE(s && s->pc.mgr, "MGRSolve before MGRSetup");
+      if (!s->pc.mgr->bound_to(A->A)) s->pc.mgr->rebind(A->A, Comm::world().size > 1 ? &A->halo : nullptr); // reused preconditioner, later system
+   });
 }
 HY_GETTER(HYPRE_MGRGetNumIterations, HYPRE_Int, s->amg_iters)
 HY_GETTER(HYPRE_MGRGetFinalRelativeResidualNorm, HYPRE_Real, s->amg_rel)
 
 HY_GETTER(HYPRE_BoomerAMGGetNumIterations, HYPRE_Int, s->amg_iters)
 HY_GETTER(HYPRE_BoomerAMGGetFinalRelativeResidualNorm, HYPRE_Real, s->amg_rel)
-HY_GETTER(HYPRE_BoomerAMGGetNumLevels, HYPRE_Int, s->amg ? s->amg->num_levels() : 0)
+HY_GETTER(HYPRE_BoomerAMGGetNumLevels, HYPRE_Int, s->pc.amg ? s->pc.amg->num_levels() : 0)
 extern "C" HYPRE_Int HYPRE_BoomerAMGGetComplexities(HYPRE_Solver s, HYPRE_Real *grid, HYPRE_Real *op)
 {
-   if (!s || !s->amg) return hypre_set_error(HYPRE_ERROR_ARG, "GetComplexities before Setup");
-   if (grid) *grid = s->amg->grid_complexity();
-   if (op) *op = s->amg->operator_complexity();
+   if (!s || !s->pc.amg) return hypre_set_error(HYPRE_ERROR_ARG, "GetComplexities before Setup");
+   if (grid) *grid = s->pc.amg->grid_complexity();
+   if (op) *op = s->pc.amg->operator_complexity();
    return 0;
 }
 

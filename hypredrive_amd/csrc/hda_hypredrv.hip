@@ -1519,7 +1519,7 @@ bool hypredrv_peek(void *obj, const DCsr **A, const HaloPlan **halo, const doubl
    if (A) *A = &h->mat_A->A;
    if (halo) *halo = &h->mat_A->halo;
    if (rhs) *rhs = h->vec_b ? (h->vec_b->ensure_device(), h->vec_b->data()) : nullptr;
-   if (amg) *amg = (h->precon && h->precon_is_setup && h->precon->kind == HDA_SOLVER_AMG) ? h->precon->amg.get() : nullptr;
+   if (amg) *amg = (h->precon && h->precon_is_setup && h->precon->kind == HDA_SOLVER_AMG) ? h->precon->pc.amg : nullptr;
    return true;
 }
 } // namespace hda
@@ -1527,14 +1527,14 @@ bool hypredrv_peek(void *obj, const DCsr **A, const HaloPlan **halo, const doubl
 extern "C" int hda_amd_partitioned_levels(void *obj)
 {
    hypredrv_struct *h = (hypredrv_struct *)obj;
-   if (!h || !h->precon || !h->precon_is_setup || !h->precon->amg) return 0;
-   return h->precon->amg->partitioned_levels();
+   if (!h || !h->precon || !h->precon_is_setup || !h->precon->pc.amg) return 0;
+   return h->precon->pc.amg->partitioned_levels();
 }
 extern "C" int hda_amd_hierarchy_levels(void *obj) // partitioned levels + the levels of the replicated tail
 {
    hypredrv_struct *h = (hypredrv_struct *)obj;
-   if (!h || !h->precon || !h->precon_is_setup || !h->precon->amg) return 0;
-   return h->precon->amg->total_levels();
+   if (!h || !h->precon || !h->precon_is_setup || !h->precon->pc.amg) return 0;
+   return h->precon->pc.amg->total_levels();
 }
 // bytes THIS rank streams per Krylov iteration (operator product + vector updates) and per
 // V-cycle with the hierarchy that was set up: [0] CSR figures of SURVEY 8(d), [1] the formats
@@ -1551,11 +1551,11 @@ extern "C" uint32_t HYPREDRV_AMD_SolvePhaseBytes(HYPREDRV_t h, double iteration[
 {
    CHECK_INIT_OBJ(h);
    API_TRY
-   if (!h->mat_A || !h->precon || !h->precon->amg) return err_set(ERR_UNKNOWN, "SolvePhaseBytes: set up the solver first");
+   if (!h->mat_A || !h->precon || !h->precon->pc.amg) return err_set(ERR_UNKNOWN, "SolvePhaseBytes: set up the solver first");
    for (int f = 0; f < 2; f++)
    {
       iteration[f] = pcg_iteration_bytes(h->mat_A->A, f == 1);
-      vcycle[f]    = h->precon->amg->vcycle_bytes(f == 1);
+      vcycle[f]    = h->precon->pc.amg->vcycle_bytes(f == 1);
    }
    API_CATCH
 }
@@ -1566,8 +1566,8 @@ extern "C" uint32_t HYPREDRV_AMD_ProbeDominant(HYPREDRV_t h, int arm, int *level
 {
    CHECK_INIT_OBJ(h);
    API_TRY
-   if (!h->mat_A || !h->precon || !h->precon->amg) return err_set(ERR_UNKNOWN, "ProbeDominant: set up the solver first");
-   Amg &amg = *h->precon->amg;
+   if (!h->mat_A || !h->precon || !h->precon->pc.amg) return err_set(ERR_UNKNOWN, "ProbeDominant: set up the solver first");
+   Amg &amg = *h->precon->pc.amg;
    if (arm)
    {
       int    best = 0;
@@ -1645,6 +1645,26 @@ static const SolverOps &solver_ops(const HYPRE_Solver s)
    }
 }
 
+// Setup and Solve of every preconditioner kind, as the reference's precon_ops (src/internal/precon.c); any other kind: BoomerAMG
+struct PreconOps {
+   int                  kind;
+   HYPRE_PtrToSolverFcn setup, solve;
+};
+static const PreconOps kPreconOps[] = {
+   {HDA_SOLVER_AMG, HYPRE_BoomerAMGSetup, HYPRE_BoomerAMGSolve}, // first: what precon_ops falls back to
+   {HDA_SOLVER_ILU, HYPRE_ILUSetup, HYPRE_ILUSolve},
+   {HDA_SOLVER_MGR, HYPRE_MGRSetup, HYPRE_MGRSolve},
+   {HDA_SOLVER_SCHWARZ, HYPRE_SchwarzSetup, HYPRE_SchwarzSolve},
+   {HDA_SOLVER_AMS, HYPRE_AMSSetup, HYPRE_AMSSolve},
+   {HDA_SOLVER_FSAI, HYPRE_FSAISetup, HYPRE_FSAISolve},
+};
+static const PreconOps &precon_ops(int kind)
+{
+   for (const PreconOps &e : kPreconOps)
+      if (e.kind == kind) return e;
+   return kPreconOps[0];
+}
+
 // reference src/internal/solver.c:268-311: the Krylov setup calls back here; the "prec"
 // timer brackets exactly the AMG setup
 static HYPRE_Int PreconSetupDispatch(HYPRE_Solver cookie, HYPRE_Matrix A, HYPRE_Vector b, HYPRE_Vector x)
@@ -1660,12 +1680,7 @@ static HYPRE_Int PreconSetupDispatch(HYPRE_Solver cookie, HYPRE_Matrix A, HYPRE_
       ams_hand_over(h);
    }
    annotate(h, "prec", true);
-   HYPRE_Int ierr = (h->precon->kind == HDA_SOLVER_ILU)   ? HYPRE_ILUSetup(h->precon, A, b, x)
-                    : (h->precon->kind == HDA_SOLVER_AMS) ? HYPRE_AMSSetup(h->precon, A, b, x)
-                    : (h->precon->kind == HDA_SOLVER_SCHWARZ) ? HYPRE_SchwarzSetup(h->precon, A, b, x)
-                    : (h->precon->kind == HDA_SOLVER_FSAI) ? HYPRE_FSAISetup(h->precon, A, b, x)
-                    : (h->precon->kind == HDA_SOLVER_MGR) ? HYPRE_MGRSetup(h->precon, A, b, x)
-                                                          : HYPRE_BoomerAMGSetup(h->precon, A, b, x);
+   HYPRE_Int ierr = precon_ops(h->precon->kind).setup(h->precon, A, b, x);
    if (hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
    annotate(h, "prec", false);
    h->precon_is_setup = (ierr == 0);
@@ -1675,12 +1690,7 @@ static HYPRE_Int PreconSetupDispatch(HYPRE_Solver cookie, HYPRE_Matrix A, HYPRE_
 static HYPRE_Int PreconSolveDispatch(HYPRE_Solver cookie, HYPRE_Matrix A, HYPRE_Vector b, HYPRE_Vector x)
 {
    hypredrv_struct *h = ((PreconCookie *)(void *)cookie)->self;
-   return (h->precon->kind == HDA_SOLVER_ILU)   ? HYPRE_ILUSolve(h->precon, A, b, x)
-          : (h->precon->kind == HDA_SOLVER_AMS) ? HYPRE_AMSSolve(h->precon, A, b, x)
-          : (h->precon->kind == HDA_SOLVER_SCHWARZ) ? HYPRE_SchwarzSolve(h->precon, A, b, x)
-          : (h->precon->kind == HDA_SOLVER_FSAI) ? HYPRE_FSAISolve(h->precon, A, b, x)
-          : (h->precon->kind == HDA_SOLVER_MGR) ? HYPRE_MGRSolve(h->precon, A, b, x)
-                                                : HYPRE_BoomerAMGSolve(h->precon, A, b, x);
+   return precon_ops(h->precon->kind).solve(h->precon, A, b, x);
 }
 
 // hypredrv_ILUCreate (reference src/internal/ilu.c:63-115): same setter sequence
@@ -2497,12 +2507,7 @@ extern "C" uint32_t HYPREDRV_PreconApply(HYPREDRV_t h, HYPRE_Vector b, HYPRE_Vec
    err_reset();
    API_TRY
    if (!h->precon || !h->precon_is_setup) return err_set(ERR_INVALID_PRECON, "PreconApply requires a set-up preconditioner");
-   if (h->precon->kind == HDA_SOLVER_ILU) HYPRE_ILUSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
-   else if (h->precon->kind == HDA_SOLVER_SCHWARZ) HYPRE_SchwarzSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
-   else if (h->precon->kind == HDA_SOLVER_FSAI) HYPRE_FSAISolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
-   else if (h->precon->kind == HDA_SOLVER_AMS) HYPRE_AMSSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
-   else if (h->precon->kind == HDA_SOLVER_MGR) HYPRE_MGRSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
-   else HYPRE_BoomerAMGSolve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
+   precon_ops(h->precon->kind).solve(h->precon, h->mat_M ? h->mat_M : h->mat_A, b, x);
    consume_hypre_errors();
    API_CATCH
 }
@@ -2631,10 +2636,10 @@ extern "C" uint32_t HYPREDRV_LinearSolverGetSolveTime(HYPREDRV_t h, double *s) {
 extern "C" int hda_amd_mgr_view(void *obj, int level, int which, long long *info, int *rowptr, int *col, double *val, long long *ghosts)
 {
    hypredrv_struct *h = (hypredrv_struct *)obj;
-   if (!h || !h->precon || !h->precon_is_setup || !h->precon->mgr || !info) return 1;
+   if (!h || !h->precon || !h->precon_is_setup || !h->precon->pc.mgr || !info) return 1;
    try
    {
-      const Mgr             &M = *h->precon->mgr;
+      const Mgr             &M = *h->precon->pc.mgr;
       const DCsr            &X = M.matrix(level, which);
       long long              r0 = 0, c0 = 0;
       std::vector<long long> g;

@@ -384,23 +384,6 @@ void Ilu::apply(const double *r, double *z)
    // upper_it - 1 swaps starting from the buffer chosen above end in z
 }
 
-// hypre_ILUSolve as hypredrive uses it (preconditioner: ilu, or stand-alone): max_iter iterations of
-// x += M^{-1} (b - A x).  x must have room for A's ghost columns when A is a row block (halo != null).
-void ilu_solve(Ilu &F, const DCsr &A, const HaloPlan *halo, const double *b, double *x, bool zero_guess, DArray<double> &r, DArray<double> &c)
-{
-   const int n = A.nrows;
-   if (r.size() < (size_t)std::max(n, 1)) r.alloc((size_t)std::max(n, 1));
-   if (c.size() < (size_t)std::max(n, 1)) c.alloc((size_t)std::max(n, 1));
-   for (int it = 0; it < std::max(F.prm.max_iter, 1); it++)
-   {
-      if (zero_guess && it == 0) { F.apply(b, x); continue; } // b - A*0 = b exactly
-      if (halo) halo_exchange(*halo, x);
-      residual(A, x, b, r.data());
-      F.apply(r.data(), c.data());
-      axpy(n, 1.0, c.data(), x);
-   }
-}
-
 // algorithmic HBM bytes of one apply (factors once per pass, vectors in and out)
 double Ilu::apply_bytes() const
 {

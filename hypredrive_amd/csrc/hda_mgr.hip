@@ -676,13 +676,13 @@ double *Mgr::cycle(int l, const double *f, double *u, bool zero)
          if (prm.ckrylov_precond && camg) M = [this](const double *r, double *z, int slot) { camg->apply(r, z, -1); if (slot >= 0) dot(Ac.nrows, r, z, slot); };
          else if (prm.ckrylov_precond && cilu)
             M = [this, multi](const double *r, double *z, int slot) {
-               ilu_solve(*cilu, Ac, multi ? &hAc : nullptr, r, z, true, cilu_r, cilu_c);
+               stationary_solve(*cilu, Ac, multi ? &hAc : nullptr, r, z, true, std::max(cilu->prm.max_iter, 1), cilu_r, cilu_c);
                if (slot >= 0) dot(Ac.nrows, r, z, slot);
             };
          nested_krylov(prm.ckrylov_method, prm.ckrylov, LinOp(Ac, multi ? &hAc : nullptr, uc.size()), M, f, u);
       }
       else if (camg) camg->apply(f, u, -1);
-      else ilu_solve(*cilu, Ac, multi ? &hAc : nullptr, f, u, true, cilu_r, cilu_c);
+      else stationary_solve(*cilu, Ac, multi ? &hAc : nullptr, f, u, true, std::max(cilu->prm.max_iter, 1), cilu_r, cilu_c);
       return u;
    }
    Level                &L = lv[(size_t)l];
@@ -696,7 +696,7 @@ double *Mgr::cycle(int l, const double *f, double *u, bool zero)
    auto global_relax = [&]() {
       if (p.grelax_type == 16)
       {
-         ilu_solve(*L.gilu, A, multi ? L.hA : nullptr, f, cur, zero, L.ilu_r, L.ilu_c);
+         stationary_solve(*L.gilu, A, multi ? L.hA : nullptr, f, cur, zero, std::max(L.gilu->prm.max_iter, 1), L.ilu_r, L.ilu_c);
          zero = false;
       }
       else if (p.grelax_type >= 0)

@@ -706,19 +706,4 @@ void Schwarz::apply(const double *r, double *z)
    else k_sw_as<<<ceil_div(n, 256), 256, 0, STREAM>>>(n, prm.weight, copy_ptr.data(), copy_pos.data(), y_ext.data(), z);
 }
 
-// max_iter iterations x += M^-1 (b - A x); from a zero guess the first one skips the product
-void schwarz_solve(Schwarz &S, const DCsr &A, const double *b, double *x, bool zero_guess, DArray<double> &r, DArray<double> &c)
-{
-   const int n = A.nrows;
-   if (r.size() < (size_t)std::max(n, 1)) r.alloc((size_t)std::max(n, 1));
-   if (c.size() < (size_t)std::max(n, 1)) c.alloc((size_t)std::max(n, 1));
-   for (int it = 0; it < std::max(S.prm.max_iter, 1); it++)
-   {
-      if (zero_guess && it == 0) { S.apply(b, x); continue; } // b - A*0 = b exactly
-      residual(A, x, b, r.data());
-      S.apply(r.data(), c.data());
-      axpy(n, 1.0, c.data(), x);
-   }
-}
-
 } // namespace hda
