@@ -79,27 +79,69 @@ class MgrLevelParams(C.Structure):
                 ("coarse_type", C.c_int), ("nonglk_max_elmts", C.c_int), ("coarse_th", C.c_double)]
 
 
-# every symbol include/hypredrv_amd.h declares (checked by tests/test_cabi_symbols.py)
-SYMBOLS = [
-    "hda_last_error", "hda_device_count", "hda_device_name", "hda_device_pci_bus_id", "hda_device_sync",
-    "hda_amg_default_params", "hda_krylov_default_params", "hda_csr_create", "hda_csr_destroy",
-    "hda_csr_dims", "hda_csr_download", "hda_lap7_create", "hda_spmv", "hda_relax", "hda_dot",
-    "hda_l1_norms", "hda_strength", "hda_pmis", "hda_interp_extpi", "hda_interp_direct", "hda_rap", "hda_transpose",
-    "hda_spgemm", "hda_amg_create", "hda_amg_destroy", "hda_amg_num_levels",
-    "hda_last_precond_calls", "hda_amg_create_dof", "hda_format_bytes", "hda_probe_spmv", "hda_probe_read", "hda_amg_level_matrix", "hda_amg_fold_sweep", "hda_amg_level_cf", "hda_amg_complexities", "hda_amg_vcycle_bytes",
-    "hda_amg_vcycle", "hda_pcg", "hda_gmres", "hda_time_kernel", "hda_solve_device",
-    "hda_pcg_iteration_bytes", "hda_memory_stats", "hda_memory_cached", "hda_memory_driver_stats", "hda_memory_trim", "hda_comm_selftest", "hda_check_row_total", "hda_ilu_create", "hda_ilu_create_blocks", "hda_ilu_blocks", "hda_ilu_factors", "hda_fgmres", "hda_bicgstab", "hda_mgr_create", "hda_mgr_matrix", "hda_mgr_blk_inverses",
-    "hda_probe_add", "hda_probe_read_id", "hda_borrow_hypredrv", "hda_comm_stats", "hda_comm_name", "hda_comm_size", "hda_halo_plan_host",
-    "hda_amd_partitioned_levels", "hda_amd_hierarchy_levels",
-    "hda_second_strength", "hda_coarsen_second_pass", "hda_interp_multipass", "hda_truncate_rows", "hda_interp_agg_two_stage",
-    "hda_interp_mm_extpi", "hda_interp_extended", "hda_interp_mm_ext", "hda_interp_one_point", "hda_interp_standard", "hda_set_overlap", "hda_marker", "hda_relax_blocks", "hda_l1_norms_blocks", "hda_hmis_blocks", "hda_amg_blocks", "hda_amg_level_blocks",
-    "hda_csr_form", "hda_spmv_mode", "hda_air_restriction",
-    "hda_cljp", "hda_rs_blocks", "hda_falgout_blocks", "hda_measure_rnd",
-    "hda_schwarz_create", "hda_schwarz_domains", "hda_schwarz_info", "hda_precond_time",
-    "hda_spgemm_last_route", "hda_sort_rows_last_route",
-    "hda_ams_default_amg_params", "hda_ams_create", "hda_ams_matrix", "hda_ams_info",
-    "hda_fsai_create", "hda_fsai_factor", "hda_fsai_info",
-]
+def _signatures():
+    """function -> (restype, argtypes) for every function include/hypredrv_amd.h declares, and for the test entries it does not"""
+    P = C.POINTER
+    I, D, S, VP, U64, I64 = C.c_int, C.c_double, C.c_char_p, C.c_void_p, C.c_uint64, C.c_int64
+    IP, DP, LP, LLP, MASK, OUT = P(I), P(D), P(I64), P(C.c_longlong), P(C.c_ubyte), P(VP)
+    AMG, KRY = P(AmgParams), P(KrylovParams)
+    interp = (I, [VP, MASK, IP, I, D, OUT])
+    krylov = (I, [VP, VP, KRY, DP, DP, DP, IP, IP, DP])
+    view = (I, [VP, I, OUT])
+    declared = {
+        "hda_last_error": (S, []), "hda_device_count": (I, []), "hda_device_name": (I, [S, I]), "hda_device_pci_bus_id": (I, [I, S, I]),
+        "hda_device_sync": (I, []), "hda_marker": (I, [I]),
+        "hda_amg_default_params": (None, [AMG]), "hda_krylov_default_params": (None, [KRY, I]),
+        "hda_csr_create": (I, [I, I, LP, LP, DP, OUT]), "hda_csr_destroy": (I, [VP]), "hda_csr_dims": (I, [VP, IP, IP, IP]),
+        "hda_csr_download": (I, [VP, IP, IP, DP]), "hda_lap7_create": (I, [IP, IP, IP, DP, OUT, DP]),
+        "hda_spmv": (I, [VP, D, DP, D, DP]), "hda_relax": (I, [VP, I, D, I, DP, DP]), "hda_dot": (I, [I, DP, DP, DP]),
+        "hda_l1_norms": (I, [VP, I, DP]),
+        "hda_relax_blocks": (I, [VP, I, D, I, I, LP, DP, DP]), "hda_l1_norms_blocks": (I, [VP, I, I, LP, DP]),
+        "hda_hmis_blocks": (I, [VP, MASK, I, LP, U64, I, IP]), "hda_cljp": (I, [VP, MASK, U64, I, I64, IP, IP]),
+        "hda_rs_blocks": (I, [VP, MASK, I, LP, IP]), "hda_falgout_blocks": (I, [VP, MASK, I, LP, U64, I, IP, IP]),
+        "hda_measure_rnd": (I, [I, U64, I, I64, DP]),
+        "hda_strength": (I, [VP, D, D, MASK]), "hda_pmis": (I, [VP, MASK, U64, I, I64, IP]),
+        "hda_interp_extpi": interp, "hda_interp_direct": interp, "hda_interp_mm_extpi": interp, "hda_interp_extended": interp,
+        "hda_interp_mm_ext": interp, "hda_interp_standard": interp, "hda_interp_one_point": (I, [VP, MASK, IP, OUT]),
+        "hda_rap": (I, [VP, VP, OUT]), "hda_air_restriction": (I, [VP, IP, I, D, D, OUT, LP]),
+        "hda_second_strength": (I, [VP, MASK, IP, I, OUT]), "hda_coarsen_second_pass": (I, [VP, MASK, I, U64, I, IP]),
+        "hda_interp_multipass": (I, [VP, MASK, IP, OUT]), "hda_truncate_rows": (I, [VP, I, D]),
+        "hda_interp_agg_two_stage": (I, [VP, MASK, IP, IP, I, I, D, I, D, OUT, OUT, OUT]),
+        "hda_transpose": (I, [VP, OUT]), "hda_spgemm": (I, [VP, VP, OUT]),
+        "hda_spgemm_last_route": (I, [LP]), "hda_sort_rows_last_route": (I, [LP]),
+        "hda_amg_create": (I, [AMG, VP, OUT]), "hda_amg_create_dof": (I, [AMG, VP, IP, OUT]), "hda_amg_destroy": (I, [VP]),
+        "hda_ilu_create": (I, [VP, I, I, I, I, OUT]), "hda_ilu_create_blocks": (I, [VP, I, I, I, I, I, LP, OUT]),
+        "hda_ilu_blocks": (I, [VP, I]), "hda_ilu_factors": view,
+        "hda_schwarz_create": (I, [VP, I, I, I, I, LP, I, D, OUT]), "hda_schwarz_domains": (I, [VP, IP, IP, IP]),
+        "hda_schwarz_info": (I, [VP, LP, DP]),
+        "hda_fsai_create": (I, [VP, I, D, I, I, I, I, LP, OUT]), "hda_fsai_factor": view, "hda_fsai_info": (I, [VP, I, LP, DP]),
+        "hda_precond_time": (I, [VP, I, DP]),
+        "hda_ams_default_amg_params": (None, [AMG, I]), "hda_ams_create": (I, [VP, VP, DP, DP, DP, I, I, I, D, I, AMG, AMG, OUT]),
+        "hda_ams_matrix": view, "hda_ams_info": (I, [VP, LP, DP]),
+        "hda_mgr_create": (I, [VP, IP, I, P(MgrLevelParams), AMG, I, OUT]), "hda_mgr_matrix": (I, [VP, I, I, OUT]),
+        "hda_mgr_blk_inverses": (I, [VP, I, I, DP, IP, IP]),
+        "hda_amg_num_levels": (I, [VP]), "hda_amg_level_matrix": (I, [VP, I, I, OUT]), "hda_amg_level_cf": (I, [VP, I, IP]),
+        "hda_amg_fold_sweep": (I, [VP, I, DP, DP, DP, DP, DP]), "hda_amg_blocks": (I, [VP]), "hda_amg_level_blocks": (I, [VP, I, LP]),
+        "hda_amg_complexities": (I, [VP, DP, DP]), "hda_amg_vcycle_bytes": (D, [VP]), "hda_amg_vcycle": (I, [VP, DP, DP]),
+        "hda_pcg": krylov, "hda_gmres": krylov, "hda_fgmres": krylov, "hda_bicgstab": krylov,
+        "hda_time_kernel": (I, [I, VP, VP, I, DP, DP]), "hda_set_overlap": (None, [I]), "hda_last_precond_calls": (I, []),
+        "hda_solve_device": (I, [VP, VP, KRY, I, DP, I, DP, IP, DP, DP, DP, DP]),
+        "hda_pcg_iteration_bytes": (D, [VP]), "hda_format_bytes": (I, [VP, VP, DP, DP, DP, IP]),
+        "hda_csr_form": (I, [VP, I, IP]), "hda_spmv_mode": (I, [VP, I, I, D, D, DP, DP, DP, DP, DP, DP, DP, DP, DP, IP]),
+        "hda_borrow_hypredrv": (I, [VP, OUT, OUT]), "hda_amd_partitioned_levels": (I, [VP]), "hda_amd_hierarchy_levels": (I, [VP]),
+        "hda_halo_plan_host": (I, [I, LLP, LLP, I, IP, IP, IP, I, IP]),
+        "hda_probe_spmv": (I, [VP, I]), "hda_probe_read": (I, [DP, IP]), "hda_probe_add": (I, [VP, I, IP]),
+        "hda_probe_read_id": (I, [I, DP, IP]),
+        "hda_comm_stats": (I, [DP, I]), "hda_comm_name": (S, []), "hda_comm_size": (I, []), "hda_comm_selftest": (I, []),
+        "hda_check_row_total": (I, [C.c_longlong, I]),
+        "hda_memory_stats": (I, [DP, DP]), "hda_memory_cached": (D, []), "hda_memory_driver_stats": (I, [DP, I]), "hda_memory_trim": (I, []),
+    }
+    undeclared = {"hda_amg_rebind": (I, [VP, VP]), "hda_amg_level0_sweep": (I, [VP, I, DP, DP, DP, DP, IP])}
+    return declared, undeclared
+
+
+_DECLARED, _UNDECLARED = _signatures()
+SYMBOLS = list(_DECLARED)  # (tests/test_cabi_symbols.py compares them with the header)
 
 
 TESTRANKS_SYMBOLS = ["hda_thread_ranks_lap7", "hda_thread_world_create", "hda_thread_world_join", "hda_thread_world_leave",
@@ -139,105 +181,9 @@ def load():
             f"{_LIBPATH} not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(the MI355X solve path has no CPU fallback)")
     L = C.CDLL(_LIBPATH)
-    P = C.POINTER
-    dp, ip, vp = P(C.c_double), P(C.c_int), C.c_void_p
-    L.hda_last_error.restype = C.c_char_p
-    L.hda_device_name.argtypes = [C.c_char_p, C.c_int]
-    L.hda_device_pci_bus_id.argtypes = [C.c_int, C.c_char_p, C.c_int]
-    L.hda_amg_default_params.argtypes = [P(AmgParams)]
-    L.hda_amg_default_params.restype = None
-    L.hda_krylov_default_params.argtypes = [P(KrylovParams), C.c_int]
-    L.hda_krylov_default_params.restype = None
-    L.hda_csr_create.argtypes = [C.c_int, C.c_int, P(C.c_int64), P(C.c_int64), dp, P(vp)]
-    L.hda_csr_destroy.argtypes = [vp]
-    L.hda_csr_dims.argtypes = [vp, ip, ip, ip]
-    L.hda_csr_download.argtypes = [vp, ip, ip, dp]
-    L.hda_lap7_create.argtypes = [ip, ip, ip, dp, P(vp), dp]
-    L.hda_spmv.argtypes = [vp, C.c_double, dp, C.c_double, dp]
-    L.hda_relax.argtypes = [vp, C.c_int, C.c_double, C.c_int, dp, dp]
-    L.hda_dot.argtypes = [C.c_int, dp, dp, dp]
-    L.hda_l1_norms.argtypes = [vp, C.c_int, dp]
-    L.hda_relax_blocks.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, P(C.c_int64), dp, dp]
-    L.hda_l1_norms_blocks.argtypes = [vp, C.c_int, C.c_int, P(C.c_int64), dp]
-    L.hda_hmis_blocks.argtypes = [vp, P(C.c_ubyte), C.c_int, P(C.c_int64), C.c_uint64, C.c_int, ip]
-    L.hda_cljp.argtypes = [vp, P(C.c_ubyte), C.c_uint64, C.c_int, C.c_int64, ip, ip]
-    L.hda_rs_blocks.argtypes = [vp, P(C.c_ubyte), C.c_int, P(C.c_int64), ip]
-    L.hda_falgout_blocks.argtypes = [vp, P(C.c_ubyte), C.c_int, P(C.c_int64), C.c_uint64, C.c_int, ip, ip]
-    L.hda_measure_rnd.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_int64, dp]
-    L.hda_amg_blocks.argtypes = [vp]
-    L.hda_marker.argtypes = [C.c_int]
-    L.hda_amg_level_blocks.argtypes = [vp, C.c_int, P(C.c_int64)]
-    L.hda_strength.argtypes = [vp, C.c_double, C.c_double, P(C.c_ubyte)]
-    L.hda_pmis.argtypes = [vp, P(C.c_ubyte), C.c_uint64, C.c_int, C.c_int64, ip]
-    L.hda_interp_extpi.argtypes = [vp, P(C.c_ubyte), ip, C.c_int, C.c_double, P(vp)]
-    L.hda_interp_direct.argtypes = [vp, P(C.c_ubyte), ip, C.c_int, C.c_double, P(vp)]
-    L.hda_interp_mm_extpi.argtypes = [vp, P(C.c_ubyte), ip, C.c_int, C.c_double, P(vp)]
-    L.hda_interp_extended.argtypes = [vp, P(C.c_ubyte), ip, C.c_int, C.c_double, P(vp)]
-    L.hda_interp_mm_ext.argtypes = [vp, P(C.c_ubyte), ip, C.c_int, C.c_double, P(vp)]
-    L.hda_interp_one_point.argtypes = [vp, P(C.c_ubyte), ip, P(vp)]
-    L.hda_interp_standard.argtypes = [vp, P(C.c_ubyte), ip, C.c_int, C.c_double, P(vp)]
-    L.hda_rap.argtypes = [vp, vp, P(vp)]
-    L.hda_second_strength.argtypes = [vp, P(C.c_ubyte), ip, C.c_int, P(vp)]
-    L.hda_coarsen_second_pass.argtypes = [vp, P(C.c_ubyte), C.c_int, C.c_uint64, C.c_int, ip]
-    L.hda_interp_multipass.argtypes = [vp, P(C.c_ubyte), ip, P(vp)]
-    L.hda_truncate_rows.argtypes = [vp, C.c_int, C.c_double]
-    L.hda_interp_agg_two_stage.argtypes = [vp, P(C.c_ubyte), ip, ip, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, P(vp), P(vp), P(vp)]
-    L.hda_transpose.argtypes = [vp, P(vp)]
-    L.hda_spgemm.argtypes = [vp, vp, P(vp)]
-    L.hda_spgemm_last_route.argtypes = [P(C.c_int64)]
-    L.hda_sort_rows_last_route.argtypes = [P(C.c_int64)]
-    L.hda_amg_create.argtypes = [P(AmgParams), vp, P(vp)]
-    L.hda_amg_destroy.argtypes = [vp]
-    L.hda_mgr_create.argtypes = [vp, ip, C.c_int, P(MgrLevelParams), P(AmgParams), C.c_int, P(vp)]
-    L.hda_mgr_matrix.argtypes = [vp, C.c_int, C.c_int, P(vp)]
-    L.hda_mgr_blk_inverses.argtypes = [vp, C.c_int, C.c_int, P(C.c_double), P(C.c_int), P(C.c_int)]
-    L.hda_ilu_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, P(vp)]
-    L.hda_ilu_factors.argtypes = [vp, C.c_int, P(vp)]
-    L.hda_ilu_create_blocks.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int64), P(vp)]
-    L.hda_ilu_blocks.argtypes = [vp, C.c_int]
-    L.hda_schwarz_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int64), C.c_int, C.c_double, P(vp)]
-    L.hda_fsai_create.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int64), P(vp)]
-    L.hda_fsai_factor.argtypes = [vp, C.c_int, P(vp)]
-    L.hda_fsai_info.argtypes = [vp, C.c_int, P(C.c_int64), P(C.c_double)]
-    L.hda_schwarz_domains.argtypes = [vp, P(C.c_int), ip, ip]
-    L.hda_schwarz_info.argtypes = [vp, P(C.c_int64), P(C.c_double)]
-    L.hda_precond_time.argtypes = [vp, C.c_int, P(C.c_double)]
-    L.hda_ams_default_amg_params.argtypes = [P(AmgParams), C.c_int]
-    L.hda_ams_default_amg_params.restype = None
-    L.hda_ams_create.argtypes = [vp, vp, dp, dp, dp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, P(AmgParams), P(AmgParams), P(vp)]
-    L.hda_ams_matrix.argtypes = [vp, C.c_int, P(vp)]
-    L.hda_ams_info.argtypes = [vp, P(C.c_int64), P(C.c_double)]
-    L.hda_set_overlap.argtypes = [C.c_int]
-    L.hda_set_overlap.restype = None
-    L.hda_amg_num_levels.argtypes = [vp]
-    L.hda_amg_level_matrix.argtypes = [vp, C.c_int, C.c_int, P(vp)]
-    L.hda_amg_level_cf.argtypes = [vp, C.c_int, ip]
-    L.hda_amg_fold_sweep.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp]
-    L.hda_amg_complexities.argtypes = [vp, dp, dp]
-    L.hda_amg_vcycle_bytes.argtypes = [vp]
-    L.hda_amg_vcycle_bytes.restype = C.c_double
-    L.hda_amg_vcycle.argtypes = [vp, dp, dp]
-    for f in (L.hda_pcg, L.hda_gmres, L.hda_fgmres, L.hda_bicgstab):
-        f.argtypes = [vp, vp, P(KrylovParams), dp, dp, dp, ip, ip, dp]
-    L.hda_time_kernel.argtypes = [C.c_int, vp, vp, C.c_int, dp, dp]
-    L.hda_solve_device.argtypes = [vp, vp, P(KrylovParams), C.c_int, dp, C.c_int, dp, ip, dp, dp, dp, dp]
-    L.hda_pcg_iteration_bytes.argtypes = [vp]
-    L.hda_pcg_iteration_bytes.restype = C.c_double
-    L.hda_memory_stats.argtypes = [dp, dp]
-    L.hda_memory_cached.restype = C.c_double
-    L.hda_memory_driver_stats.argtypes = [C.POINTER(C.c_double), C.c_int]
-    L.hda_check_row_total.argtypes = [C.c_longlong, C.c_int]
-    L.hda_format_bytes.argtypes = [vp, vp, dp, dp, dp, ip]
-    L.hda_probe_spmv.argtypes = [vp, C.c_int]
-    L.hda_csr_form.argtypes = [vp, C.c_int, ip]
-    L.hda_air_restriction.argtypes = [vp, ip, C.c_int, C.c_double, C.c_double, P(vp), P(C.c_int64)]
-    L.hda_spmv_mode.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, dp, dp, dp, dp, dp, dp, dp, dp, dp, ip]
-    L.hda_probe_read.argtypes = [dp, ip]
-    L.hda_probe_add.argtypes = [vp, C.c_int, ip]
-    L.hda_probe_read_id.argtypes = [C.c_int, dp, ip]
-    L.hda_borrow_hypredrv.argtypes = [vp, P(vp), P(vp)]
-    L.hda_comm_stats.argtypes = [dp, C.c_int]
-    L.hda_comm_name.restype = C.c_char_p
+    for name, (restype, argtypes) in {**_DECLARED, **_UNDECLARED}.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _L = L
     return L
 
@@ -253,6 +199,34 @@ def _dp(a):
 
 def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+# staging of the kernel-level entries: the C side reads exactly nnz mask bytes / nrows markers, so the arrays go as they are (the
+# pointer keeps its array alive)
+def _mask(smask):
+    return np.ascontiguousarray(smask, dtype=np.uint8).ctypes.data_as(C.POINTER(C.c_ubyte))
+
+
+def _marker(cf):
+    return _ip(np.ascontiguousarray(cf, dtype=np.int32))
+
+
+def _blocks(part):
+    """(nblk, pointer to the nblk + 1 int64 row starts)"""
+    pt = np.ascontiguousarray(part, dtype=np.int64)
+    return len(pt) - 1, pt.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def _blocks_or(blocks, block_part):
+    """(blocks, NULL) unless block_part names the row starts"""
+    return (blocks, None) if block_part is None else _blocks(block_part)
+
+
+def _new_csr(fn, *args, **how):
+    """call an entry whose last argument is the new matrix handle; how: owned=False, keep=... for a borrowed view"""
+    out = C.c_void_p()
+    _check(fn(*args, C.byref(out)))
+    return Csr(out, **how)
 
 
 def device_count():
@@ -284,10 +258,7 @@ class Csr:
         rp = np.ascontiguousarray(rowptr, dtype=np.int64)
         cj = np.ascontiguousarray(cols, dtype=np.int64)
         v = np.ascontiguousarray(vals, dtype=np.float64)
-        out = C.c_void_p()
-        _check(load().hda_csr_create(nrows, ncols, rp.ctypes.data_as(C.POINTER(C.c_int64)),
-                                     cj.ctypes.data_as(C.POINTER(C.c_int64)), _dp(v), C.byref(out)))
-        return Csr(out)
+        return _new_csr(load().hda_csr_create, nrows, ncols, rp.ctypes.data_as(C.POINTER(C.c_int64)), cj.ctypes.data_as(C.POINTER(C.c_int64)), _dp(v))
 
     @staticmethod
     def from_scipy(m):
@@ -307,10 +278,10 @@ class Csr:
     def download(self):
         n, m, nnz = self.dims
         rp = np.zeros(n + 1, dtype=np.int32)
-        cj = np.zeros(max(nnz, 1), dtype=np.int32)
-        v = np.zeros(max(nnz, 1), dtype=np.float64)
+        cj = np.zeros(nnz, dtype=np.int32)
+        v = np.zeros(nnz, dtype=np.float64)
         _check(load().hda_csr_download(self.h, _ip(rp), _ip(cj), _dp(v)))
-        return rp, cj[:nnz], v[:nnz]
+        return rp, cj, v
 
     def to_scipy(self):
         import scipy.sparse as sp
@@ -339,160 +310,104 @@ class Csr:
     def relax_blocks(self, b, x, part, relax_type=13, weight=1.0, sweeps=1):
         b = np.ascontiguousarray(b, dtype=np.float64)
         x = np.ascontiguousarray(x, dtype=np.float64).copy()
-        pt = np.ascontiguousarray(part, dtype=np.int64)
-        _check(load().hda_relax_blocks(self.h, relax_type, weight, sweeps, len(pt) - 1, pt.ctypes.data_as(C.POINTER(C.c_int64)), _dp(b), _dp(x)))
+        _check(load().hda_relax_blocks(self.h, relax_type, weight, sweeps, *_blocks(part), _dp(b), _dp(x)))
         return x
 
     def l1_norms_blocks(self, option, part):
-        out = np.zeros(max(self.nrows, 1))
-        pt = np.ascontiguousarray(part, dtype=np.int64)
-        _check(load().hda_l1_norms_blocks(self.h, option, len(pt) - 1, pt.ctypes.data_as(C.POINTER(C.c_int64)), _dp(out)))
-        return out[:self.nrows]
+        out = np.zeros(self.nrows)
+        _check(load().hda_l1_norms_blocks(self.h, option, *_blocks(part), _dp(out)))
+        return out
 
     def hmis_blocks(self, smask, part, seed=2747, level=0):
-        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
-        cf = np.zeros(max(self.nrows, 1), dtype=np.int32)
-        pt = np.ascontiguousarray(part, dtype=np.int64)
-        _check(load().hda_hmis_blocks(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), len(pt) - 1, pt.ctypes.data_as(C.POINTER(C.c_int64)),
-                                      seed, level, _ip(cf)))
-        return cf[:self.nrows]
+        cf = np.zeros(self.nrows, dtype=np.int32)
+        _check(load().hda_hmis_blocks(self.h, _mask(smask), *_blocks(part), seed, level, _ip(cf)))
+        return cf
 
     # coarsen types 0 / 1 / 6; last_rounds: the CLJP rounds of the latest cljp / falgout_blocks call
     def cljp(self, smask, seed=2747, level=0, row_offset=0):
-        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
-        cf = np.zeros(max(self.nrows, 1), dtype=np.int32)
+        cf = np.zeros(self.nrows, dtype=np.int32)
         rounds = C.c_int(0)
-        _check(load().hda_cljp(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), seed, level, row_offset, _ip(cf), C.byref(rounds)))
+        _check(load().hda_cljp(self.h, _mask(smask), seed, level, row_offset, _ip(cf), C.byref(rounds)))
         self.last_rounds = rounds.value
-        return cf[:self.nrows]
+        return cf
 
     def rs_blocks(self, smask, part=None):
-        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
-        cf = np.zeros(max(self.nrows, 1), dtype=np.int32)
-        pt = np.ascontiguousarray([0, self.nrows] if part is None else part, dtype=np.int64)
-        _check(load().hda_rs_blocks(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), len(pt) - 1, pt.ctypes.data_as(C.POINTER(C.c_int64)), _ip(cf)))
-        return cf[:self.nrows]
+        cf = np.zeros(self.nrows, dtype=np.int32)
+        _check(load().hda_rs_blocks(self.h, _mask(smask), *_blocks([0, self.nrows] if part is None else part), _ip(cf)))
+        return cf
 
     def falgout_blocks(self, smask, part=None, seed=2747, level=0):
-        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
-        cf = np.zeros(max(self.nrows, 1), dtype=np.int32)
-        pt = np.ascontiguousarray([0, self.nrows] if part is None else part, dtype=np.int64)
+        cf = np.zeros(self.nrows, dtype=np.int32)
         rounds = C.c_int(0)
-        _check(load().hda_falgout_blocks(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), len(pt) - 1, pt.ctypes.data_as(C.POINTER(C.c_int64)),
-                                         seed, level, _ip(cf), C.byref(rounds)))
+        _check(load().hda_falgout_blocks(self.h, _mask(smask), *_blocks([0, self.nrows] if part is None else part), seed, level, _ip(cf),
+                                         C.byref(rounds)))
         self.last_rounds = rounds.value
-        return cf[:self.nrows]
+        return cf
 
     def strength(self, theta=0.25, max_row_sum=0.9):
-        sm = np.zeros(max(self.nnz, 1), dtype=np.uint8)
+        sm = np.zeros(self.nnz, dtype=np.uint8)
         _check(load().hda_strength(self.h, theta, max_row_sum, sm.ctypes.data_as(C.POINTER(C.c_ubyte))))
-        return sm[:self.nnz]
+        return sm
 
     def pmis(self, smask, seed=2747, level=0, row_offset=0):
-        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
-        cf = np.zeros(max(self.nrows, 1), dtype=np.int32)
-        _check(load().hda_pmis(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), seed, level, row_offset, _ip(cf)))
-        return cf[:self.nrows]
+        cf = np.zeros(self.nrows, dtype=np.int32)
+        _check(load().hda_pmis(self.h, _mask(smask), seed, level, row_offset, _ip(cf)))
+        return cf
 
     def interp_extpi(self, smask, cf, pmax=4, trunc_factor=0.0):
-        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
-        cfa = np.ascontiguousarray(np.concatenate([cf, np.zeros(1, np.int32)]), dtype=np.int32)
-        out = C.c_void_p()
-        _check(load().hda_interp_extpi(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), _ip(cfa), pmax,
-                                       trunc_factor, C.byref(out)))
-        return Csr(out)
+        return _new_csr(load().hda_interp_extpi, self.h, _mask(smask), _marker(cf), pmax, trunc_factor)
 
     def interp_mm_extpi(self, smask, cf, pmax=4, trunc_factor=0.0):
         """interpolation type 17 (mm-ext+i): the matrix-matrix form of extended+i"""
-        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
-        cfa = np.ascontiguousarray(np.concatenate([cf, np.zeros(1, np.int32)]), dtype=np.int32)
-        out = C.c_void_p()
-        _check(load().hda_interp_mm_extpi(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), _ip(cfa), pmax, trunc_factor, C.byref(out)))
-        return Csr(out)
+        return _new_csr(load().hda_interp_mm_extpi, self.h, _mask(smask), _marker(cf), pmax, trunc_factor)
 
     def interp_extended(self, smask, cf, pmax=4, trunc_factor=0.0):
         """interpolation type 14 (extended): extended+i without the point itself in its strong F neighbours' denominators"""
-        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
-        cfa = np.ascontiguousarray(np.concatenate([cf, np.zeros(1, np.int32)]), dtype=np.int32)
-        out = C.c_void_p()
-        _check(load().hda_interp_extended(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), _ip(cfa), pmax, trunc_factor, C.byref(out)))
-        return Csr(out)
+        return _new_csr(load().hda_interp_extended, self.h, _mask(smask), _marker(cf), pmax, trunc_factor)
 
     def interp_mm_ext(self, smask, cf, pmax=4, trunc_factor=0.0):
         """interpolation type 16 (mm_extended): mm-ext+i with s_ki := 0"""
-        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
-        cfa = np.ascontiguousarray(np.concatenate([cf, np.zeros(1, np.int32)]), dtype=np.int32)
-        out = C.c_void_p()
-        _check(load().hda_interp_mm_ext(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), _ip(cfa), pmax, trunc_factor, C.byref(out)))
-        return Csr(out)
+        return _new_csr(load().hda_interp_mm_ext, self.h, _mask(smask), _marker(cf), pmax, trunc_factor)
 
     def interp_one_point(self, smask, cf):
         """interpolation type 100 (one_point): weight 1 towards the strong C neighbour of largest |a_ij|"""
-        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
-        cfa = np.ascontiguousarray(np.concatenate([cf, np.zeros(1, np.int32)]), dtype=np.int32)
-        out = C.c_void_p()
-        _check(load().hda_interp_one_point(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), _ip(cfa), C.byref(out)))
-        return Csr(out)
+        return _new_csr(load().hda_interp_one_point, self.h, _mask(smask), _marker(cf))
 
     def interp_standard(self, smask, cf, pmax=4, trunc_factor=0.0):
         """interpolation type 8 (standard): strong F neighbours eliminated through their own rows, direct interpolation on the result"""
-        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
-        cfa = np.ascontiguousarray(np.concatenate([cf, np.zeros(1, np.int32)]), dtype=np.int32)
-        out = C.c_void_p()
-        _check(load().hda_interp_standard(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), _ip(cfa), pmax, trunc_factor, C.byref(out)))
-        return Csr(out)
+        return _new_csr(load().hda_interp_standard, self.h, _mask(smask), _marker(cf), pmax, trunc_factor)
 
     def interp_direct(self, smask, cf, pmax=4, trunc_factor=0.0):
         """interpolation type 3 (direct_sep_weights)"""
-        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
-        cfa = np.ascontiguousarray(np.concatenate([cf, np.zeros(1, np.int32)]), dtype=np.int32)
-        out = C.c_void_p()
-        _check(load().hda_interp_direct(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), _ip(cfa), pmax,
-                                        trunc_factor, C.byref(out)))
-        return Csr(out)
+        return _new_csr(load().hda_interp_direct, self.h, _mask(smask), _marker(cf), pmax, trunc_factor)
 
     def second_strength(self, smask, cf, num_paths=1):
         """aggressive coarsening: strong connections of distance <= 2 among the C points of cf (values = number of paths)"""
-        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
-        cfa = np.ascontiguousarray(np.concatenate([cf, np.zeros(1, np.int32)]), dtype=np.int32)
-        out = C.c_void_p()
-        _check(load().hda_second_strength(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), _ip(cfa), num_paths, C.byref(out)))
-        return Csr(out)
+        return _new_csr(load().hda_second_strength, self.h, _mask(smask), _marker(cf), num_paths)
 
     def coarsen_second_pass(self, smask, cf, num_paths=1, seed=2747, level=0):
         """aggressive coarsening: the second PMIS pass; returns the updated C/F marker"""
-        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
-        cfa = np.ascontiguousarray(np.concatenate([cf, np.zeros(1, np.int32)]), dtype=np.int32)
-        _check(load().hda_coarsen_second_pass(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), num_paths, seed, level, _ip(cfa)))
-        return cfa[:-1].copy()
+        cfa = np.array(cf, dtype=np.int32)  # (a copy: the pass updates it in place)
+        _check(load().hda_coarsen_second_pass(self.h, _mask(smask), num_paths, seed, level, _ip(cfa)))
+        return cfa
 
     def interp_multipass(self, smask, cf):
         """aggressive coarsening: multipass interpolation (aggressive.prolongation_type 4)"""
-        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
-        cfa = np.ascontiguousarray(np.concatenate([cf, np.zeros(1, np.int32)]), dtype=np.int32)
-        out = C.c_void_p()
-        _check(load().hda_interp_multipass(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), _ip(cfa), C.byref(out)))
-        return Csr(out)
+        return _new_csr(load().hda_interp_multipass, self.h, _mask(smask), _marker(cf))
 
     def interp_agg_two_stage_parts(self, smask, cf1, cf2, plus_i=False, p12_pmax=0, p12_tf=0.0, pmax=0, tf=0.0):
         """aggressive.prolongation_type 5 (plus_i False: mm_extended) / 6 (True: mm_extended+i): (P1, P2, P) with P = P1 P2.  cf1: the
         splitting after the first coarsening pass, cf2: after coarsen_second_pass; P1 (n x |C1|) is truncated by p12_pmax / p12_tf,
         P2 (|C1| x |C2|) by pmax / tf."""
-        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
-        c1 = np.ascontiguousarray(np.concatenate([cf1, np.zeros(1, np.int32)]), dtype=np.int32)
-        c2 = np.ascontiguousarray(np.concatenate([cf2, np.zeros(1, np.int32)]), dtype=np.int32)
         o1, o2, o = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _check(load().hda_interp_agg_two_stage(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), _ip(c1), _ip(c2), 1 if plus_i else 0,
+        _check(load().hda_interp_agg_two_stage(self.h, _mask(smask), _marker(cf1), _marker(cf2), 1 if plus_i else 0,
                                                int(p12_pmax), float(p12_tf), int(pmax), float(tf), C.byref(o1), C.byref(o2), C.byref(o)))
         return Csr(o1), Csr(o2), Csr(o)
 
     def interp_agg_second_stage(self, smask, cf1, cf2, plus_i=False, pmax=0, tf=0.0):
         """P2 alone (only the |C1| rows of the second stage are built)"""
-        sm = np.ascontiguousarray(np.concatenate([smask, np.zeros(1, np.uint8)]), dtype=np.uint8)
-        c1 = np.ascontiguousarray(np.concatenate([cf1, np.zeros(1, np.int32)]), dtype=np.int32)
-        c2 = np.ascontiguousarray(np.concatenate([cf2, np.zeros(1, np.int32)]), dtype=np.int32)
         o2 = C.c_void_p()
-        _check(load().hda_interp_agg_two_stage(self.h, sm.ctypes.data_as(C.POINTER(C.c_ubyte)), _ip(c1), _ip(c2), 1 if plus_i else 0,
+        _check(load().hda_interp_agg_two_stage(self.h, _mask(smask), _marker(cf1), _marker(cf2), 1 if plus_i else 0,
                                                0, 0.0, int(pmax), float(tf), None, C.byref(o2), None))
         return Csr(o2)
 
@@ -506,19 +421,13 @@ class Csr:
         return self
 
     def rap(self, P):
-        out = C.c_void_p()
-        _check(load().hda_rap(self.h, P.h, C.byref(out)))
-        return Csr(out)
+        return _new_csr(load().hda_rap, self.h, P.h)
 
     def transpose(self):
-        out = C.c_void_p()
-        _check(load().hda_transpose(self.h, C.byref(out)))
-        return Csr(out)
+        return _new_csr(load().hda_transpose, self.h)
 
     def matmul(self, Y):
-        out = C.c_void_p()
-        _check(load().hda_spgemm(self.h, Y.h, C.byref(out)))
-        return Csr(out)
+        return _new_csr(load().hda_spgemm, self.h, Y.h)
 
 
 SPGEMM_PATHS = ("none", "esc", "hash")
@@ -565,8 +474,7 @@ class Amg:
         if dof is None:
             _check(load().hda_amg_create(C.byref(self.params), A.h, C.byref(self.h)))
         else:
-            d = np.ascontiguousarray(dof, dtype=np.int32)
-            _check(load().hda_amg_create_dof(C.byref(self.params), A.h, d.ctypes.data_as(C.POINTER(C.c_int)), C.byref(self.h)))
+            _check(load().hda_amg_create_dof(C.byref(self.params), A.h, _marker(dof), C.byref(self.h)))
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -578,9 +486,7 @@ class Amg:
         return load().hda_amg_num_levels(self.h)
 
     def level_matrix(self, level, which=0):
-        out = C.c_void_p()
-        _check(load().hda_amg_level_matrix(self.h, level, which, C.byref(out)))
-        return Csr(out, owned=False, keep=self)
+        return _new_csr(load().hda_amg_level_matrix, self.h, level, which, owned=False, keep=self)
 
     def fold_sweep(self, level, dinv, t, e, u):
         """The folded up-leg sweep of a folded level as the cycle launches it: (u + dinv * t) + Pt e, Pt = level_matrix(level, 3)."""
@@ -595,30 +501,21 @@ class Amg:
         """One Jacobi sweep on level 0 as the cycle launches it: (x + dinv (b - A x), <b, out> or None, divisors read by row class?)."""
         b, x = (np.ascontiguousarray(v, dtype=np.float64) for v in (b, x))
         out, dot, by_class = np.zeros_like(b), C.c_double(), C.c_int()
-        L = load()
-        L.hda_amg_level0_sweep.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                           C.POINTER(C.c_double), C.POINTER(C.c_int)]
-        _check(L.hda_amg_level0_sweep(self.h, direction, _dp(b), _dp(x), _dp(out), C.byref(dot) if want_dot else None, C.byref(by_class)))
+        _check(load().hda_amg_level0_sweep(self.h, direction, _dp(b), _dp(x), _dp(out), C.byref(dot) if want_dot else None, C.byref(by_class)))
         return out, (dot.value if want_dot else None), bool(by_class.value)
 
     def rebind(self, A):
         """Level 0 on another matrix of the same size; divisors and coarse levels are kept (preconditioner reuse)."""
-        L = load()
-        L.hda_amg_rebind.argtypes = [C.c_void_p, C.c_void_p]
-        _check(L.hda_amg_rebind(self.h, A.h))
+        _check(load().hda_amg_rebind(self.h, A.h))
         self.A = A
 
     def ilu_factors(self, level):
         """Factors of the complex smoother (amg.smoother.type ilu) of a level."""
-        out = C.c_void_p()
-        _check(load().hda_ilu_factors(self.h, level, C.byref(out)))
-        return Csr(out, owned=False, keep=self)
+        return _new_csr(load().hda_ilu_factors, self.h, level, owned=False, keep=self)
 
     def fsai_factor(self, level):
         """G of the static FSAI smoother (amg.smoother.type fsai) of a level."""
-        out = C.c_void_p()
-        _check(load().hda_fsai_factor(self.h, level, C.byref(out)))
-        return Csr(out, owned=False, keep=self)
+        return _new_csr(load().hda_fsai_factor, self.h, level, owned=False, keep=self)
 
     def fsai_info(self, level):
         return _fsai_info(self.h, level)
@@ -730,9 +627,7 @@ class Mgr:
             self.h = None
 
     def matrix(self, level, which=0):
-        out = C.c_void_p()
-        _check(load().hda_mgr_matrix(self.h, level, which, C.byref(out)))
-        return Csr(out, owned=False, keep=self)
+        return _new_csr(load().hda_mgr_matrix, self.h, level, which, owned=False, keep=self)
 
     def block_inverses(self, level, tier=0):
         """F-block inverses of a reduction level as an array (nblk, b, b), and nf (the short last block: its top-left corner)"""
@@ -762,12 +657,7 @@ class Ilu:
         if blocks == 1 and block_part is None:
             _check(load().hda_ilu_create(A.h, max_iter, tri_solve, lower_it, upper_it, C.byref(self.h)))
         else:
-            bp = None
-            if block_part is not None:
-                bp = np.ascontiguousarray(block_part, dtype=np.int64)
-                blocks = len(bp) - 1
-            _check(load().hda_ilu_create_blocks(A.h, max_iter, tri_solve, lower_it, upper_it, blocks,
-                                                None if bp is None else bp.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(self.h)))
+            _check(load().hda_ilu_create_blocks(A.h, max_iter, tri_solve, lower_it, upper_it, *_blocks_or(blocks, block_part), C.byref(self.h)))
 
     @property
     def blocks(self):
@@ -780,9 +670,7 @@ class Ilu:
 
     @property
     def factors(self):
-        out = C.c_void_p()
-        _check(load().hda_ilu_factors(self.h, -1, C.byref(out)))
-        return Csr(out, owned=False, keep=self)
+        return _new_csr(load().hda_ilu_factors, self.h, -1, owned=False, keep=self)
 
     def apply(self, r):
         """One application from a zero guess (max_iter iterations x += M^-1 (r - A x))."""
@@ -803,12 +691,8 @@ class Schwarz:
         """blocks: 1 one block, 0 the setup's choice, V the even split unless block_part names the V + 1 row starts"""
         self.A = A
         self.h = C.c_void_p()
-        bp = None
-        if block_part is not None:
-            bp = np.ascontiguousarray(block_part, dtype=np.int64)
-            blocks = len(bp) - 1
-        _check(load().hda_schwarz_create(A.h, SCHWARZ_VARIANTS[variant] if isinstance(variant, str) else int(variant), overlap, fill, blocks,
-                                         None if bp is None else bp.ctypes.data_as(C.POINTER(C.c_int64)), max_iter, weight, C.byref(self.h)))
+        _check(load().hda_schwarz_create(A.h, SCHWARZ_VARIANTS[variant] if isinstance(variant, str) else int(variant), overlap, fill,
+                                         *_blocks_or(blocks, block_part), max_iter, weight, C.byref(self.h)))
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -832,9 +716,7 @@ class Schwarz:
 
     def factors(self):
         """Block-diagonal factors of all subdomains in the extended numbering (strict lower part L with unit diagonal, rest U)."""
-        out = C.c_void_p()
-        _check(load().hda_ilu_factors(self.h, -1, C.byref(out)))
-        return Csr(out, owned=False, keep=self)
+        return _new_csr(load().hda_ilu_factors, self.h, -1, owned=False, keep=self)
 
     def apply(self, r):
         """One application from a zero guess (max_iter iterations x += M^-1 (r - A x))."""
@@ -859,12 +741,8 @@ class Fsai:
         """blocks: 1 one block, 0 the setup's choice, V the even split unless block_part names the V + 1 row starts"""
         self.A = A
         self.h = C.c_void_p()
-        bp = None
-        if block_part is not None:
-            bp = np.ascontiguousarray(block_part, dtype=np.int64)
-            blocks = len(bp) - 1
-        _check(load().hda_fsai_create(A.h, num_levels, threshold, max_nnz_row, eig_max_iters, max_iter, blocks,
-                                      None if bp is None else bp.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(self.h)))
+        _check(load().hda_fsai_create(A.h, num_levels, threshold, max_nnz_row, eig_max_iters, max_iter, *_blocks_or(blocks, block_part),
+                                      C.byref(self.h)))
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -873,9 +751,7 @@ class Fsai:
 
     def factor(self):
         """G: rows column-sorted, the diagonal last"""
-        out = C.c_void_p()
-        _check(load().hda_fsai_factor(self.h, -1, C.byref(out)))
-        return Csr(out, owned=False, keep=self)
+        return _new_csr(load().hda_fsai_factor, self.h, -1, owned=False, keep=self)
 
     def info(self):
         """dict: n, nnz_factor, fallback_rows, blocks, class_rows (rows per lane class), omega, apply_bytes, setup_ms"""
@@ -928,9 +804,7 @@ class Ams:
             self.h = None
 
     def _matrix(self, which):
-        out = C.c_void_p()
-        _check(load().hda_ams_matrix(self.h, which, C.byref(out)))
-        return Csr(out, owned=False, keep=self)
+        return _new_csr(load().hda_ams_matrix, self.h, which, owned=False, keep=self)
 
     def pi(self):
         return self._matrix(0)
@@ -1034,10 +908,9 @@ def air_restriction(A, cf, distance=2, strong_th=0.25, filter_th=0.0):
     """Approximate ideal restriction (restriction_type air_1 / air_2) of the square operator A for the splitting cf
     (> 0 C, < 0 F), built on the device.  Returns (R, stats): R a Csr (C points x rows), stats dict(fallback, max_m, small, mid,
     large) -- rows that fell back to injection, the largest neighbourhood, C rows solved by each tier."""
-    cfa = np.ascontiguousarray(np.concatenate([np.asarray(cf, dtype=np.int32), np.zeros(1, np.int32)]), dtype=np.int32)
     st = np.zeros(5, dtype=np.int64)
     out = C.c_void_p()
-    _check(load().hda_air_restriction(A.h, _ip(cfa), int(distance), float(strong_th), float(filter_th), C.byref(out),
+    _check(load().hda_air_restriction(A.h, _marker(cf), int(distance), float(strong_th), float(filter_th), C.byref(out),
                                       st.ctypes.data_as(C.POINTER(C.c_int64))))
     return Csr(out), dict(fallback=int(st[0]), max_m=int(st[1]), small=int(st[2]), mid=int(st[3]), large=int(st[4]))
 
@@ -1181,7 +1054,6 @@ def run_thread_ranks(nranks, body):
 
 
 def comm_name():
-    load().hda_comm_name.restype = C.c_char_p
     return load().hda_comm_name().decode()
 
 
@@ -1214,9 +1086,9 @@ def memory_trim():
 
 def measure_rnd(n, seed=2747, level=0, row_offset=0):
     """The random part in [0, 1) of the coarsening measures of n rows (the stream of PMIS, HMIS, CLJP and Falgout)."""
-    out = np.zeros(max(n, 1))
+    out = np.zeros(max(n, 0))  # (a negative n is the library's to refuse)
     _check(load().hda_measure_rnd(n, seed, level, row_offset, _dp(out)))
-    return out[:n]
+    return out
 
 
 def sync():

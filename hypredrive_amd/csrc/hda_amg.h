@@ -172,6 +172,14 @@ void two_stage_build(const DCsr &A, const std::vector<int> &part, TwoStage &ts);
 void two_stage_sweep(const DCsr &A, const TwoStage &ts, const double *dinv, double weight, const double *b, double *u, double *r, double *z,
                      int terms, bool zero_guess, const HaloPlan *halo = nullptr);
 
+// the relaxation types of the AMG cycle by class, and the divisors of a sweep (hda_amg_setup.hip; the kernel-level relax entries use the
+// same): dinv = weight / d with d the l1 row sum (18), the option-4 l1 norm on the row blocks d_part (8 / 13 / 14) or a_ii (the rest)
+bool is_jacobi_type(int t);    // 0, 7, 18
+bool is_gs_type(int t);        // 3, 4, 6, 8, 13, 14 (hybrid Gauss-Seidel)
+bool is_l1_gs_type(int t);     // 8, 13, 14
+bool is_two_stage_type(int t); // 11, 12
+void build_dinv(const DCsr &A, int relax_type, double weight, DArray<double> &dinv, const int *d_part = nullptr, int nblk = 0);
+
 // block-Jacobi ILU(0) of a rank's diagonal block (hda_ilu.hip)
 class Ilu {
  public:

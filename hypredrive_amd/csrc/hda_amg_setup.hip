@@ -2917,12 +2917,12 @@ void amg_rap(const DCsr &A, const DCsr &P, const DCsr &R, DCsr &Ac, DCsr *AP_out
 
 // --------------------------------------------------------------- hierarchy
 
-static bool is_jacobi_type(int t) { return t == 18 || t == 0 || t == 7; }
-static bool is_gs_type(int t) { return t == 3 || t == 4 || t == 6 || t == 8 || t == 13 || t == 14; }
-static bool is_l1_gs_type(int t) { return t == 8 || t == 13 || t == 14; }
+bool is_jacobi_type(int t) { return t == 18 || t == 0 || t == 7; }
+bool is_gs_type(int t) { return t == 3 || t == 4 || t == 6 || t == 8 || t == 13 || t == 14; }
+bool is_l1_gs_type(int t) { return t == 8 || t == 13 || t == 14; }
 // two-stage Gauss-Seidel (hda_twostage.hip): 11 = one term of the Neumann series of (D + L)^-1 after the Jacobi term, 12 = two.  Not
 // a hybrid Gauss-Seidel type: no level sets, no automatic row blocks; explicit row blocks restrict L to the row's block
-static bool is_two_stage_type(int t) { return t == 11 || t == 12; }
+bool is_two_stage_type(int t) { return t == 11 || t == 12; }
 
 // divisor of the sweep: l1 row sums (18), hypre's "option 4" l1 (13/14/8: a_ii plus half the
 // off-rank row sum) or the plain diagonal (0/7/3/4/6/11/12).  Extracting the diagonal is option 4
@@ -2934,7 +2934,7 @@ static bool same_divisors(int t1, int t2)
    auto cls = [](int t) { return t == 18 ? 1 : is_l1_gs_type(t) ? 2 : 0; };
    return cls(t1) == cls(t2);
 }
-static void build_dinv(const DCsr &A, int relax_type, double weight, DArray<double> &dinv, const int *d_part = nullptr, int nblk = 0)
+void build_dinv(const DCsr &A, int relax_type, double weight, DArray<double> &dinv, const int *d_part, int nblk)
 {
    DArray<double> d((size_t)std::max(A.nrows, 1));
    dinv.alloc((size_t)std::max(A.nrows, 1));

@@ -171,6 +171,43 @@ static KrylovParams to_kparams(const hda_krylov_params *p)
    return k;
 }
 
+// ---- staging: how every kernel-level entry point below moves host buffers in and out, and hands out matrices
+// n host values in a device array of max(n, len, 1) elements: exactly n are read from the caller, whatever lies beyond them is zero
+template <class T>
+static DArray<T> staged(const T *host, int n, int len = 0)
+{
+   DArray<T> d((size_t)std::max({n, len, 1}));
+   if (d.size() > (size_t)std::max(n, 0)) d.zero();
+   if (n > 0) HDA_HIP(hipMemcpyAsync(d.data(), host, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, Context::get().stream));
+   Context::get().sync(); // host buffer may be pageable / transient
+   return d;
+}
+// room for n results ...
+template <class T>
+static DArray<T> room(int n) { return DArray<T>((size_t)std::max(n, 1)); }
+// ... and exactly n of them back to the caller
+template <class T>
+static void fetch(const T *dev, T *host, int n)
+{
+   if (n > 0) HDA_HIP(hipMemcpyAsync(host, dev, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, Context::get().stream));
+   Context::get().sync();
+}
+// a new matrix, built on the stream, becomes the caller's
+static void finish(std::unique_ptr<hda_csr_s> &h, hda_csr_t *out)
+{
+   Context::get().sync();
+   *out = h.release();
+}
+// a borrowed view of a matrix that lives in the preconditioner of h; the handle keeps the view
+static void lend(hda_amg_t h, const DCsr *m, hda_csr_t *out)
+{
+   auto v      = std::make_unique<hda_csr_s>();
+   v->borrowed = true;
+   v->ref      = m;
+   *out        = v.get();
+   h->views.push_back(std::move(v));
+}
+
 // ------------------------------------------------------------------ matrices
 
 __global__ void k_cols64_to_32(long nnz, const long long *__restrict__ in, long long offset, int *__restrict__ out)
@@ -205,8 +242,7 @@ extern "C" int hda_csr_create(int nrows, int ncols, const int64_t *rowptr, const
       h->m.val.upload(vals + base, (size_t)nnz);
    }
    sort_rows(h->m);
-   Context::get().sync();
-   *out = h.release();
+   finish(h, out);
    HDA_CATCH
 }
 
@@ -257,8 +293,7 @@ extern "C" int hda_lap7_create(const int n[3], const int P[3], const int pc[3], 
    k_cols64_to_32<<<2048, 256, 0, Context::get().stream>>>(nnz, cols64.data(), 0, h->m.col.data());
    sort_rows(h->m);
    if (rhs_host) h->rhs.download(rhs_host, (size_t)N);
-   Context::get().sync();
-   *A = h.release();
+   finish(h, A);
    HDA_CATCH
 }
 
@@ -267,31 +302,24 @@ extern "C" int hda_lap7_create(const int n[3], const int P[3], const int pc[3], 
 extern "C" int hda_spmv(hda_csr_t A, double alpha, const double *x, double beta, double *y)
 {
    HDA_TRY
-   const DCsr    &m = A->get();
-   DArray<double> dx, dy;
-   dx.upload(x, (size_t)m.ncols);
-   dy.upload(y, (size_t)m.nrows);
+   const DCsr    &m  = A->get();
+   DArray<double> dx = staged(x, m.ncols), dy = staged(y, m.nrows);
    spmv(m, alpha, dx.data(), beta, dy.data(), dy.data());
-   dy.download(y, (size_t)m.nrows);
+   fetch(dy.data(), y, m.nrows);
    HDA_CATCH
 }
 
 extern "C" int hda_relax(hda_csr_t A, int relax_type, double weight, int sweeps, const double *b, double *x)
 {
    HDA_TRY
-   const DCsr &m      = A->get();
-   const bool  jacobi_t = relax_type == 18 || relax_type == 0 || relax_type == 7;
-   const bool  gs_t     = relax_type == 3 || relax_type == 4 || relax_type == 6 || relax_type == 8 || relax_type == 13 || relax_type == 14;
-   const bool  ts_t     = relax_type == 11 || relax_type == 12;
+   const DCsr &m        = A->get();
+   const bool  jacobi_t = is_jacobi_type(relax_type), gs_t = is_gs_type(relax_type), ts_t = is_two_stage_type(relax_type);
    HDA_REQUIRE(jacobi_t || gs_t || ts_t, "device relax: Jacobi (0/7/18), hybrid Gauss-Seidel (3/4/6/8/13/14) or two-stage Gauss-Seidel (11/12)");
-   DArray<double> d((size_t)std::max(m.nrows, 1)), dinv((size_t)std::max(m.nrows, 1)), db, x0, x1;
-   if (relax_type == 18) l1_row_norms(m, 1, d.data());
-   else if (relax_type == 13 || relax_type == 14 || relax_type == 8) l1_row_norms(m, 4, d.data());
-   else extract_diag(m, d.data());
-   make_dinv(m.nrows, d.data(), weight, dinv.data());
-   db.upload(b, (size_t)m.nrows);
-   x0.upload(x, (size_t)std::max(m.ncols, m.nrows));
-   x1.alloc((size_t)std::max(m.ncols, m.nrows));
+   const bool     fwd = relax_type != 4 && relax_type != 14, bwd = relax_type != 3 && relax_type != 13; // the symmetric types sweep both ways
+   DArray<double> dinv;
+   build_dinv(m, relax_type, weight, dinv);
+   const int      nx = std::max(m.ncols, m.nrows);
+   DArray<double> db = staged(b, m.nrows), x0 = staged(x, m.nrows, nx), x1 = room<double>(nx);
    double *cur = x0.data(), *alt = x1.data();
    GsPlan  plan;
    if (gs_t) build_gs_plan(m, plan);
@@ -300,7 +328,7 @@ extern "C" int hda_relax(hda_csr_t A, int relax_type, double weight, int sweeps,
    if (ts_t)
    {
       two_stage_build(m, {}, ts);
-      if (relax_type == 12) tz.alloc((size_t)std::max(m.nrows, 1));
+      if (relax_type == 12) tz = room<double>(m.nrows);
    }
    for (int s = 0; s < sweeps; s++)
    {
@@ -312,12 +340,11 @@ extern "C" int hda_relax(hda_csr_t A, int relax_type, double weight, int sweeps,
       }
       else
       {
-         if (relax_type == 3 || relax_type == 13 || relax_type == 6 || relax_type == 8) gs_sweep(m, plan, dinv.data(), db.data(), cur, true);
-         if (relax_type == 4 || relax_type == 14 || relax_type == 6 || relax_type == 8) gs_sweep(m, plan, dinv.data(), db.data(), cur, false);
+         if (fwd) gs_sweep(m, plan, dinv.data(), db.data(), cur, true);
+         if (bwd) gs_sweep(m, plan, dinv.data(), db.data(), cur, false);
       }
    }
-   HDA_HIP(hipMemcpyAsync(x, cur, sizeof(double) * (size_t)m.nrows, hipMemcpyDeviceToHost, Context::get().stream));
-   Context::get().sync();
+   fetch(cur, x, m.nrows);
    gs_free_check(); // (an aborted barrier-free sweep is reported by the call that ran it, not by a later solve)
    HDA_CATCH
 }
@@ -326,51 +353,42 @@ extern "C" int hda_relax_blocks(hda_csr_t A, int relax_type, double weight, int 
 {
    HDA_TRY
    const DCsr &m    = A->get();
-   const bool  gs_t = relax_type == 3 || relax_type == 4 || relax_type == 6 || relax_type == 8 || relax_type == 13 || relax_type == 14;
-   const bool  ts_t = relax_type == 11 || relax_type == 12;
+   const bool  gs_t = is_gs_type(relax_type), ts_t = is_two_stage_type(relax_type);
    HDA_REQUIRE(gs_t || ts_t, "row-block relax: hybrid Gauss-Seidel (3/4/6/8/13/14) or two-stage Gauss-Seidel (11/12)");
    const std::vector<int> hp = to_part(nblk, part, m.nrows);
+   const int              nx = std::max(m.ncols, m.nrows);
+   DArray<double>         dinv;
    if (ts_t)
    { // L restricted to every row's block; the divisors are the plain diagonal whatever the blocks
       TwoStage ts;
       two_stage_build(m, hp, ts);
-      DArray<double> d((size_t)std::max(m.nrows, 1)), dinv((size_t)std::max(m.nrows, 1)), db, x0, r, tz;
-      extract_diag(m, d.data());
-      make_dinv(m.nrows, d.data(), weight, dinv.data());
-      db.upload(b, (size_t)m.nrows);
-      x0.upload(x, (size_t)std::max(m.ncols, m.nrows));
-      r.alloc((size_t)std::max(m.nrows, 1));
-      if (relax_type == 12) tz.alloc((size_t)std::max(m.nrows, 1));
+      build_dinv(m, relax_type, weight, dinv);
+      DArray<double> db = staged(b, m.nrows), x0 = staged(x, m.nrows, nx), r = room<double>(m.nrows), tz;
+      if (relax_type == 12) tz = room<double>(m.nrows);
       for (int s = 0; s < sweeps; s++) two_stage_sweep(m, ts, dinv.data(), weight, db.data(), x0.data(), r.data(), tz.data(), relax_type == 11 ? 1 : 2, false);
-      HDA_HIP(hipMemcpyAsync(x, x0.data(), sizeof(double) * (size_t)m.nrows, hipMemcpyDeviceToHost, Context::get().stream));
-      Context::get().sync();
+      fetch(x0.data(), x, m.nrows);
       return HDA_OK;
    }
    GsPlan plan;
    build_gs_plan_blocks(m, hp, plan);
-   DArray<double> d((size_t)std::max(m.nrows, 1)), dinv((size_t)std::max(m.nrows, 1)), db, x0, x1;
-   if (relax_type == 13 || relax_type == 14 || relax_type == 8) l1_row_norms(m, 4, d.data(), plan.blk_part.data(), nblk);
-   else extract_diag(m, d.data());
-   make_dinv(m.nrows, d.data(), weight, dinv.data());
-   db.upload(b, (size_t)m.nrows);
-   x0.upload(x, (size_t)std::max(m.ncols, m.nrows));
-   x1.alloc((size_t)std::max(m.ncols, m.nrows));
+   build_dinv(m, relax_type, weight, dinv, plan.blk_part.data(), nblk);
+   DArray<double> db = staged(b, m.nrows), x0 = staged(x, m.nrows, nx), x1 = room<double>(nx);
    double *cur = x0.data(), *alt = x1.data();
+   const bool fwd = relax_type != 4 && relax_type != 14, bwd = relax_type != 3 && relax_type != 13; // the symmetric types sweep both ways
    for (int s = 0; s < sweeps; s++)
    {
-      if (relax_type == 3 || relax_type == 13 || relax_type == 6 || relax_type == 8)
+      if (fwd)
       {
          gs_sweep_blocks(m, plan, dinv.data(), db.data(), cur, alt, true, false);
          std::swap(cur, alt);
       }
-      if (relax_type == 4 || relax_type == 14 || relax_type == 6 || relax_type == 8)
+      if (bwd)
       {
          gs_sweep_blocks(m, plan, dinv.data(), db.data(), cur, alt, false, false);
          std::swap(cur, alt);
       }
    }
-   HDA_HIP(hipMemcpyAsync(x, cur, sizeof(double) * (size_t)m.nrows, hipMemcpyDeviceToHost, Context::get().stream));
-   Context::get().sync();
+   fetch(cur, x, m.nrows);
    gs_free_check();
    HDA_CATCH
 }
@@ -380,11 +398,10 @@ extern "C" int hda_l1_norms_blocks(hda_csr_t A, int option, int nblk, const int6
    HDA_TRY
    const DCsr            &m  = A->get();
    const std::vector<int> hp = to_part(nblk, part, m.nrows);
-   DArray<int>            dp;
-   dp.upload(hp.data(), hp.size());
-   DArray<double> d((size_t)std::max(m.nrows, 1));
+   DArray<int>            dp = staged(hp.data(), (int)hp.size());
+   DArray<double>         d  = room<double>(m.nrows);
    l1_row_norms(m, option, d.data(), dp.data(), nblk);
-   if (m.nrows) d.download(l1, (size_t)m.nrows);
+   fetch(d.data(), l1, m.nrows);
    HDA_CATCH
 }
 
@@ -393,11 +410,10 @@ extern "C" int hda_hmis_blocks(hda_csr_t A, const unsigned char *smask, int nblk
    HDA_TRY
    const DCsr            &m  = A->get();
    const std::vector<int> hp = to_part(nblk, part, m.nrows);
-   DArray<unsigned char>  sm((size_t)std::max(m.nnz, 1));
-   if (m.nnz) sm.upload(smask, (size_t)m.nnz);
-   DArray<int> dcf((size_t)std::max(m.nrows, 1));
+   DArray<unsigned char>  sm  = staged(smask, m.nnz);
+   DArray<int>            dcf = room<int>(m.nrows);
    amg_hmis(m, sm.data(), hp, seed, level, dcf.data());
-   if (m.nrows) dcf.download(cf, (size_t)m.nrows);
+   fetch(dcf.data(), cf, m.nrows);
    HDA_CATCH
 }
 
@@ -405,13 +421,12 @@ extern "C" int hda_hmis_blocks(hda_csr_t A, const unsigned char *smask, int nblk
 extern "C" int hda_cljp(hda_csr_t A, const unsigned char *smask, uint64_t seed, int level, int64_t row_offset, int *cf, int *rounds)
 {
    HDA_TRY
-   const DCsr           &m = A->get();
-   DArray<unsigned char> sm((size_t)std::max(m.nnz, 1));
-   if (m.nnz) sm.upload(smask, (size_t)m.nnz);
-   DArray<int> dcf((size_t)std::max(m.nrows, 1));
-   const int   r = amg_cljp(m, sm.data(), seed, level, row_offset, dcf.data());
+   const DCsr           &m   = A->get();
+   DArray<unsigned char> sm  = staged(smask, m.nnz);
+   DArray<int>           dcf = room<int>(m.nrows);
+   const int             r   = amg_cljp(m, sm.data(), seed, level, row_offset, dcf.data());
    if (rounds) *rounds = r;
-   if (m.nrows) dcf.download(cf, (size_t)m.nrows);
+   fetch(dcf.data(), cf, m.nrows);
    HDA_CATCH
 }
 
@@ -420,11 +435,10 @@ extern "C" int hda_rs_blocks(hda_csr_t A, const unsigned char *smask, int nblk, 
    HDA_TRY
    const DCsr            &m  = A->get();
    const std::vector<int> hp = to_part(nblk, part, m.nrows);
-   DArray<unsigned char>  sm((size_t)std::max(m.nnz, 1));
-   if (m.nnz) sm.upload(smask, (size_t)m.nnz);
-   DArray<int> dcf((size_t)std::max(m.nrows, 1));
+   DArray<unsigned char>  sm  = staged(smask, m.nnz);
+   DArray<int>            dcf = room<int>(m.nrows);
    amg_rs(m, sm.data(), hp, dcf.data());
-   if (m.nrows) dcf.download(cf, (size_t)m.nrows);
+   fetch(dcf.data(), cf, m.nrows);
    HDA_CATCH
 }
 
@@ -434,12 +448,11 @@ extern "C" int hda_falgout_blocks(hda_csr_t A, const unsigned char *smask, int n
    HDA_TRY
    const DCsr            &m  = A->get();
    const std::vector<int> hp = to_part(nblk, part, m.nrows);
-   DArray<unsigned char>  sm((size_t)std::max(m.nnz, 1));
-   if (m.nnz) sm.upload(smask, (size_t)m.nnz);
-   DArray<int> dcf((size_t)std::max(m.nrows, 1));
-   const int   r = amg_falgout(m, sm.data(), hp, seed, level, dcf.data());
+   DArray<unsigned char>  sm  = staged(smask, m.nnz);
+   DArray<int>            dcf = room<int>(m.nrows);
+   const int              r   = amg_falgout(m, sm.data(), hp, seed, level, dcf.data());
    if (rounds) *rounds = r;
-   if (m.nrows) dcf.download(cf, (size_t)m.nrows);
+   fetch(dcf.data(), cf, m.nrows);
    HDA_CATCH
 }
 
@@ -447,18 +460,16 @@ extern "C" int hda_measure_rnd(int n, uint64_t seed, int level, int64_t row_offs
 {
    HDA_TRY
    HDA_REQUIRE(n >= 0, "hda_measure_rnd: negative length");
-   DArray<double> d((size_t)std::max(n, 1));
+   DArray<double> d = room<double>(n);
    amg_measure_rnd(n, seed, level, row_offset, d.data());
-   if (n) d.download(rnd, (size_t)n);
+   fetch(d.data(), rnd, n);
    HDA_CATCH
 }
 
 extern "C" int hda_dot(int n, const double *x, const double *y, double *result)
 {
    HDA_TRY
-   DArray<double> dx, dy;
-   dx.upload(x, (size_t)n);
-   dy.upload(y, (size_t)n);
+   DArray<double> dx = staged(x, n), dy = staged(y, n);
    dot(n, dx.data(), dy.data(), 0);
    finalize(0, S_TMP);
    *result = read_scalar(S_TMP);
@@ -469,9 +480,9 @@ extern "C" int hda_l1_norms(hda_csr_t A, int option, double *l1)
 {
    HDA_TRY
    const DCsr    &m = A->get();
-   DArray<double> d((size_t)m.nrows);
+   DArray<double> d = room<double>(m.nrows);
    l1_row_norms(m, option, d.data());
-   d.download(l1, (size_t)m.nrows);
+   fetch(d.data(), l1, m.nrows);
    HDA_CATCH
 }
 
@@ -480,10 +491,10 @@ extern "C" int hda_l1_norms(hda_csr_t A, int option, double *l1)
 extern "C" int hda_strength(hda_csr_t A, double theta, double max_row_sum, unsigned char *smask)
 {
    HDA_TRY
-   const DCsr           &m = A->get();
-   DArray<unsigned char> sm((size_t)std::max(m.nnz, 1));
+   const DCsr           &m  = A->get();
+   DArray<unsigned char> sm = room<unsigned char>(m.nnz);
    amg_strength(m, theta, max_row_sum, sm.data());
-   if (m.nnz) sm.download(smask, (size_t)m.nnz);
+   fetch(sm.data(), smask, m.nnz);
    HDA_CATCH
 }
 
@@ -491,91 +502,42 @@ extern "C" int hda_pmis(hda_csr_t A, const unsigned char *smask, uint64_t seed, 
                         int64_t row_offset, int *cf)
 {
    HDA_TRY
-   const DCsr           &m = A->get();
-   DArray<unsigned char> sm;
-   sm.upload(smask, (size_t)std::max(m.nnz, 1));
-   DArray<int> dcf((size_t)std::max(m.nrows, 1));
+   const DCsr           &m   = A->get();
+   DArray<unsigned char> sm  = staged(smask, m.nnz);
+   DArray<int>           dcf = room<int>(m.nrows);
    amg_pmis(m, sm.data(), seed, level, row_offset, dcf.data());
-   if (m.nrows) dcf.download(cf, (size_t)m.nrows);
+   fetch(dcf.data(), cf, m.nrows);
    HDA_CATCH
 }
 
-extern "C" int hda_interp_extpi(hda_csr_t A, const unsigned char *smask, const int *cf, int pmax,
-                                double trunc_factor, hda_csr_t *P)
-{
-   HDA_TRY
-   const DCsr           &m = A->get();
-   DArray<unsigned char> sm;
-   DArray<int>           dcf;
-   sm.upload(smask, (size_t)std::max(m.nnz, 1));
-   dcf.upload(cf, (size_t)std::max(m.nrows, 1));
-   auto h = std::make_unique<hda_csr_s>();
-   amg_interp_extpi(m, sm.data(), dcf.data(), pmax, trunc_factor, h->m);
-   Context::get().sync();
-   *P = h.release();
-   HDA_CATCH
-}
-
-extern "C" int hda_interp_direct(hda_csr_t A, const unsigned char *smask, const int *cf, int pmax,
-                                 double trunc_factor, hda_csr_t *P)
-{
-   HDA_TRY
-   const DCsr           &m = A->get();
-   DArray<unsigned char> sm;
-   DArray<int>           dcf;
-   sm.upload(smask, (size_t)std::max(m.nnz, 1));
-   dcf.upload(cf, (size_t)std::max(m.nrows, 1));
-   auto h = std::make_unique<hda_csr_s>();
-   amg_interp_extpi(m, sm.data(), dcf.data(), pmax, trunc_factor, h->m, nullptr, 3);
-   Context::get().sync();
-   *P = h.release();
-   HDA_CATCH
-}
-
-extern "C" int hda_interp_standard(hda_csr_t A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, hda_csr_t *P)
-{
-   HDA_TRY
-   const DCsr           &m = A->get();
-   DArray<unsigned char> sm;
-   DArray<int>           dcf;
-   sm.upload(smask, (size_t)std::max(m.nnz, 1));
-   dcf.upload(cf, (size_t)std::max(m.nrows, 1));
-   auto h = std::make_unique<hda_csr_s>();
-   amg_interp_extpi(m, sm.data(), dcf.data(), pmax, trunc_factor, h->m, nullptr, 8);
-   Context::get().sync();
-   *P = h.release();
-   HDA_CATCH
-}
-
-extern "C" int hda_interp_mm_extpi(hda_csr_t A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, hda_csr_t *P)
-{
-   HDA_TRY
-   const DCsr           &m = A->get();
-   DArray<unsigned char> sm;
-   DArray<int>           dcf;
-   sm.upload(smask, (size_t)std::max(m.nnz, 1));
-   dcf.upload(cf, (size_t)std::max(m.nrows, 1));
-   auto h = std::make_unique<hda_csr_s>();
-   amg_interp_extpi(m, sm.data(), dcf.data(), pmax, trunc_factor, h->m, nullptr, 17);
-   Context::get().sync();
-   *P = h.release();
-   HDA_CATCH
-}
-
-// extended (14), mm-ext (16) and one-point (100) interpolation for a given strength mask and splitting
+// extended+i (6), direct (3), standard (8), mm-ext+i (17), extended (14), mm-ext (16) and one-point (100) interpolation for a given
+// strength mask and splitting
 static int interp_of_type(int interp_type, hda_csr_t A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, hda_csr_t *P)
 {
    HDA_TRY
-   const DCsr           &m = A->get();
-   DArray<unsigned char> sm;
-   DArray<int>           dcf;
-   sm.upload(smask, (size_t)std::max(m.nnz, 1));
-   dcf.upload(cf, (size_t)std::max(m.nrows, 1));
-   auto h = std::make_unique<hda_csr_s>();
+   const DCsr           &m   = A->get();
+   DArray<unsigned char> sm  = staged(smask, m.nnz);
+   DArray<int>           dcf = staged(cf, m.nrows);
+   auto                  h   = std::make_unique<hda_csr_s>();
    amg_interp_extpi(m, sm.data(), dcf.data(), pmax, trunc_factor, h->m, nullptr, interp_type);
-   Context::get().sync();
-   *P = h.release();
+   finish(h, P);
    HDA_CATCH
+}
+extern "C" int hda_interp_extpi(hda_csr_t A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, hda_csr_t *P)
+{
+   return interp_of_type(6, A, smask, cf, pmax, trunc_factor, P);
+}
+extern "C" int hda_interp_direct(hda_csr_t A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, hda_csr_t *P)
+{
+   return interp_of_type(3, A, smask, cf, pmax, trunc_factor, P);
+}
+extern "C" int hda_interp_standard(hda_csr_t A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, hda_csr_t *P)
+{
+   return interp_of_type(8, A, smask, cf, pmax, trunc_factor, P);
+}
+extern "C" int hda_interp_mm_extpi(hda_csr_t A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, hda_csr_t *P)
+{
+   return interp_of_type(17, A, smask, cf, pmax, trunc_factor, P);
 }
 extern "C" int hda_interp_extended(hda_csr_t A, const unsigned char *smask, const int *cf, int pmax, double trunc_factor, hda_csr_t *P)
 {
@@ -594,41 +556,33 @@ extern "C" int hda_interp_one_point(hda_csr_t A, const unsigned char *smask, con
 extern "C" int hda_second_strength(hda_csr_t A, const unsigned char *smask, const int *cf, int num_paths, hda_csr_t *S2)
 {
    HDA_TRY
-   const DCsr           &m = A->get();
-   DArray<unsigned char> sm;
-   DArray<int>           dcf, c1;
-   sm.upload(smask, (size_t)std::max(m.nnz, 1));
-   dcf.upload(cf, (size_t)std::max(m.nrows, 1));
-   auto h = std::make_unique<hda_csr_s>();
+   const DCsr           &m   = A->get();
+   DArray<unsigned char> sm  = staged(smask, m.nnz);
+   DArray<int>           dcf = staged(cf, m.nrows), c1;
+   auto                  h   = std::make_unique<hda_csr_s>();
    amg_second_strength(m, sm.data(), dcf.data(), num_paths, h->m, c1);
-   Context::get().sync();
-   *S2 = h.release();
+   finish(h, S2);
    HDA_CATCH
 }
 extern "C" int hda_coarsen_second_pass(hda_csr_t A, const unsigned char *smask, int num_paths, uint64_t seed, int level, int *cf)
 {
    HDA_TRY
-   const DCsr           &m = A->get();
-   DArray<unsigned char> sm;
-   DArray<int>           dcf;
-   sm.upload(smask, (size_t)std::max(m.nnz, 1));
-   dcf.upload(cf, (size_t)std::max(m.nrows, 1));
+   const DCsr           &m   = A->get();
+   DArray<unsigned char> sm  = staged(smask, m.nnz);
+   DArray<int>           dcf = staged(cf, m.nrows);
    amg_coarsen_second_pass(m, sm.data(), num_paths, seed, level, dcf.data());
-   dcf.download(cf, (size_t)m.nrows);
+   fetch(dcf.data(), cf, m.nrows);
    HDA_CATCH
 }
 extern "C" int hda_interp_multipass(hda_csr_t A, const unsigned char *smask, const int *cf, hda_csr_t *P)
 {
    HDA_TRY
-   const DCsr           &m = A->get();
-   DArray<unsigned char> sm;
-   DArray<int>           dcf;
-   sm.upload(smask, (size_t)std::max(m.nnz, 1));
-   dcf.upload(cf, (size_t)std::max(m.nrows, 1));
-   auto h = std::make_unique<hda_csr_s>();
+   const DCsr           &m   = A->get();
+   DArray<unsigned char> sm  = staged(smask, m.nnz);
+   DArray<int>           dcf = staged(cf, m.nrows);
+   auto                  h   = std::make_unique<hda_csr_s>();
    amg_interp_multipass(m, sm.data(), dcf.data(), h->m);
-   Context::get().sync();
-   *P = h.release();
+   finish(h, P);
    HDA_CATCH
 }
 
@@ -638,12 +592,9 @@ extern "C" int hda_interp_agg_two_stage(hda_csr_t A, const unsigned char *smask,
 {
    HDA_TRY
    HDA_REQUIRE(A && smask && cf1 && cf2, "hda_interp_agg_two_stage: A, smask, cf1 and cf2 are required");
-   const DCsr           &m = A->get();
-   DArray<unsigned char> sm;
-   DArray<int>           d1, d2;
-   sm.upload(smask, (size_t)std::max(m.nnz, 1));
-   d1.upload(cf1, (size_t)std::max(m.nrows, 1));
-   d2.upload(cf2, (size_t)std::max(m.nrows, 1));
+   const DCsr           &m  = A->get();
+   DArray<unsigned char> sm = staged(smask, m.nnz);
+   DArray<int>           d1 = staged(cf1, m.nrows), d2 = staged(cf2, m.nrows);
    auto h1 = std::make_unique<hda_csr_s>(), h2 = std::make_unique<hda_csr_s>(), h = std::make_unique<hda_csr_s>();
    if (!P1 && !P) amg_interp_mm_partial(m, sm.data(), d1.data(), d2.data(), pmax, trunc_factor, plus_i != 0, h2->m); // the second stage alone
    else amg_interp_agg_two_stage(m, sm.data(), d1.data(), d2.data(), plus_i != 0, p12_pmax, p12_trunc_factor, pmax, trunc_factor, h->m, &h1->m, &h2->m);
@@ -667,8 +618,7 @@ extern "C" int hda_transpose(hda_csr_t A, hda_csr_t *T)
    HDA_TRY
    auto h = std::make_unique<hda_csr_s>();
    transpose(A->get(), h->m);
-   Context::get().sync();
-   *T = h.release();
+   finish(h, T);
    HDA_CATCH
 }
 
@@ -677,8 +627,7 @@ extern "C" int hda_spgemm(hda_csr_t X, hda_csr_t Y, hda_csr_t *C)
    HDA_TRY
    auto h = std::make_unique<hda_csr_s>();
    spgemm(X->get(), Y->get(), h->m);
-   Context::get().sync();
-   *C = h.release();
+   finish(h, C);
    HDA_CATCH
 }
 
@@ -707,8 +656,7 @@ extern "C" int hda_rap(hda_csr_t A, hda_csr_t P, hda_csr_t *Ac)
    transpose(P->get(), R);
    auto h = std::make_unique<hda_csr_s>();
    amg_rap(A->get(), P->get(), R, h->m);
-   Context::get().sync();
-   *Ac = h.release();
+   finish(h, Ac);
    HDA_CATCH
 }
 
@@ -722,14 +670,12 @@ extern "C" int hda_air_restriction(hda_csr_t A, const int *cf, int distance, dou
    HDA_REQUIRE(distance == 1 || distance == 2, "hda_air_restriction: distance must be 1 (air_1) or 2 (air_2)");
    HDA_REQUIRE(std::isfinite(strong_th) && strong_th >= 0.0 && std::isfinite(filter_th) && filter_th >= 0.0,
                "hda_air_restriction: strong_th and filter_th must be finite and >= 0");
-   DArray<int> dcf;
-   dcf.upload(cf, (size_t)m.nrows);
-   auto      h = std::make_unique<hda_csr_s>();
-   long long st[5];
+   DArray<int> dcf = staged(cf, m.nrows);
+   auto        h   = std::make_unique<hda_csr_s>();
+   long long   st[5];
    air_restriction(m, m.nrows ? dcf.data() : nullptr, distance, strong_th, filter_th, h->m, st);
-   Context::get().sync();
+   finish(h, R);
    for (int q = 0; q < 5; q++) stats[q] = st[q];
-   *R = h.release();
    HDA_CATCH
 }
 
@@ -863,11 +809,7 @@ extern "C" int hda_fsai_factor(hda_amg_t h, int level, hda_csr_t *out)
    HDA_TRY
    const Fsai *F = fsai_of(h, level);
    HDA_REQUIRE(F && out, "no FSAI factor on this handle / level");
-   auto v      = std::make_unique<hda_csr_s>();
-   v->borrowed = true;
-   v->ref      = &F->factor();
-   *out        = v.get();
-   h->views.push_back(std::move(v));
+   lend(h, &F->factor(), out);
    HDA_CATCH
 }
 extern "C" int hda_fsai_info(hda_amg_t h, int level, int64_t info[9], double vals[6])
@@ -911,7 +853,7 @@ extern "C" int hda_ams_create(hda_csr_t A, hda_csr_t G, const double *c0, const 
    const double  *hc[3] = {c0, c1, c2}, *dc[3] = {nullptr, nullptr, nullptr};
    for (int k = 0; k < dimension && k < 3; k++)
    {
-      c[k].upload(hc[k], (size_t)std::max(g.ncols, 0));
+      c[k]  = staged(hc[k], g.ncols);
       dc[k] = c[k].data();
    }
    auto h = std::make_unique<hda_amg_s>();
@@ -927,11 +869,7 @@ extern "C" int hda_ams_matrix(hda_amg_t h, int which, hda_csr_t *out)
    HDA_TRY
    HDA_REQUIRE(h && h->pc.ams && out, "not an AMS handle");
    HDA_REQUIRE(which >= 0 && which <= 2, "which: 0 Pi, 1 G^T A G, 2 Pi^T A Pi");
-   auto v      = std::make_unique<hda_csr_s>();
-   v->borrowed = true;
-   v->ref      = (which == 0) ? &h->pc.ams->pi() : (which == 1) ? &h->pc.ams->a_g() : &h->pc.ams->a_pi();
-   *out        = v.get();
-   h->views.push_back(std::move(v));
+   lend(h, (which == 0) ? &h->pc.ams->pi() : (which == 1) ? &h->pc.ams->a_g() : &h->pc.ams->a_pi(), out);
    HDA_CATCH
 }
 extern "C" int hda_ams_info(hda_amg_t h, int64_t info[8], double ms[5])
@@ -1041,11 +979,7 @@ extern "C" int hda_mgr_matrix(hda_amg_t h, int level, int which, hda_csr_t *out)
 {
    HDA_TRY
    HDA_REQUIRE(h && h->pc.mgr, "not an MGR handle");
-   auto v      = std::make_unique<hda_csr_s>();
-   v->borrowed = true;
-   v->ref      = &h->pc.mgr->matrix(level, which);
-   *out        = v.get();
-   h->views.push_back(std::move(v));
+   lend(h, &h->pc.mgr->matrix(level, which), out);
    HDA_CATCH
 }
 extern "C" int hda_mgr_blk_inverses(hda_amg_t h, int level, int tier, double *out, int *b, int *nf)
@@ -1074,11 +1008,7 @@ extern "C" int hda_ilu_factors(hda_amg_t h, int level, hda_csr_t *out)
    const Ilu *F = nullptr;
    if (level < 0 && h->pc.schwarz)
    { // the block-diagonal factors of all subdomains, extended numbering
-      auto v      = std::make_unique<hda_csr_s>();
-      v->borrowed = true;
-      v->ref      = &h->pc.schwarz->factors();
-      *out        = v.get();
-      h->views.push_back(std::move(v));
+      lend(h, &h->pc.schwarz->factors(), out);
       return HDA_OK;
    }
    if (level < 0) F = h->pc.ilu.get();
@@ -1088,11 +1018,7 @@ extern "C" int hda_ilu_factors(hda_amg_t h, int level, hda_csr_t *out)
       F = h->pc.amg->level(level).ilu.get();
    }
    HDA_REQUIRE(F, "no ILU factorisation on this handle / level");
-   auto v      = std::make_unique<hda_csr_s>();
-   v->borrowed = true;
-   v->ref      = &F->factors();
-   *out        = v.get();
-   h->views.push_back(std::move(v));
+   lend(h, &F->factors(), out);
    HDA_CATCH
 }
 
@@ -1109,11 +1035,7 @@ extern "C" int hda_amg_level_matrix(hda_amg_t h, int level, int which, hda_csr_t
       HDA_REQUIRE(which != 3 || h->pc.amg->level_folded(level), "the up leg of this level is not folded");
       m = (which == 1) ? &h->pc.amg->level(level).P : (which == 2) ? &h->pc.amg->level(level).R : &h->pc.amg->level(level).Pt;
    }
-   auto v      = std::make_unique<hda_csr_s>();
-   v->borrowed = true;
-   v->ref      = m;
-   *out        = v.get();
-   h->views.push_back(std::move(v));
+   lend(h, m, out);
    HDA_CATCH
 }
 extern "C" int hda_amg_fold_sweep(hda_amg_t h, int level, const double *dinv, const double *t, const double *e, const double *u, double *out)
@@ -1121,15 +1043,11 @@ extern "C" int hda_amg_fold_sweep(hda_amg_t h, int level, const double *dinv, co
    HDA_TRY
    HDA_REQUIRE(h && h->pc.amg && dinv && t && e && u && out, "hda_amg_fold_sweep: null argument");
    HDA_REQUIRE(h->pc.amg->level_folded(level), "the up leg of this level is not folded");
-   const DCsr    &A = h->pc.amg->level_A(level), &M = h->pc.amg->level(level).Pt;
-   DArray<double> dd, dt, de, du, dout((size_t)M.nrows);
-   dd.upload(dinv, (size_t)M.nrows);
-   dt.upload(t, (size_t)M.nrows);
-   de.upload(e, (size_t)M.ncols);
-   du.upload(u, (size_t)M.nrows);
-   dout.upload(out, (size_t)M.nrows); // rows the sweep leaves alone come back as they were given
+   const DCsr    &A  = h->pc.amg->level_A(level), &M = h->pc.amg->level(level).Pt;
+   DArray<double> dd = staged(dinv, M.nrows), dt = staged(t, M.nrows), de = staged(e, M.ncols), du = staged(u, M.nrows);
+   DArray<double> dout = staged(out, M.nrows); // rows the sweep leaves alone come back as they were given
    jacobi_folded(A, M, dd.data(), dt.data(), de.data(), du.data(), dout.data());
-   dout.download(out, (size_t)M.nrows);
+   fetch(dout.data(), out, M.nrows);
    HDA_CATCH
 }
 // one level-0 Jacobi sweep as the cycle launches it (Amg::level0_sweep); *dot (may be null): <b, out> from the sweep's fused partials;
@@ -1139,17 +1057,14 @@ extern "C" int hda_amg_level0_sweep(hda_amg_t h, int dir, const double *b, const
    HDA_TRY
    HDA_REQUIRE(h && h->pc.amg && b && x && out && by_class, "hda_amg_level0_sweep: null argument");
    const DCsr    &A = h->pc.amg->level_A(0);
-   DArray<double> db, dx((size_t)std::max(A.ncols, A.nrows)), dout((size_t)A.nrows);
-   db.upload(b, (size_t)A.nrows);
-   dx.zero();
-   dx.upload(x, (size_t)A.nrows);
+   DArray<double> db = staged(b, A.nrows), dx = staged(x, A.nrows, A.ncols), dout = room<double>(A.nrows);
    *by_class = h->pc.amg->level0_sweep(dir, db.data(), dx.data(), dout.data(), dot ? 0 : -1) ? 1 : 0;
    if (dot)
    {
       finalize(0, S_TMP);
       *dot = read_scalar(S_TMP);
    }
-   dout.download(out, (size_t)A.nrows);
+   fetch(dout.data(), out, A.nrows);
    HDA_CATCH
 }
 // the hierarchy's level 0 on another matrix of the same size, divisors and coarse levels kept (Amg::rebind: preconditioner reuse)
@@ -1191,10 +1106,9 @@ extern "C" int hda_amg_vcycle(hda_amg_t h, const double *b, double *x)
 { // one application of the preconditioner from a zero guess
    HDA_TRY
    const DCsr    &m = h->pc.amg ? h->pc.amg->level_A(0) : h->A->get();
-   DArray<double> db, dx(std::max(h->pc.vec_len(m), (size_t)std::max(m.ncols, 1)));
-   db.upload(b, (size_t)m.nrows);
+   DArray<double> db = staged(b, m.nrows), dx = room<double>(std::max((int)h->pc.vec_len(m), m.ncols));
    h->pc.solve(m, nullptr, db.data(), dx.data(), true);
-   dx.download(x, (size_t)m.nrows);
+   fetch(dx.data(), x, m.nrows);
    gs_free_check();
    HDA_CATCH
 }
@@ -1206,19 +1120,14 @@ static int run_krylov(int kind, hda_csr_t A, hda_amg_t amg, const hda_krylov_par
 {
    HDA_TRY
    const DCsr    &m = A->get();
-   DArray<double> db, dx;
-   db.upload(b, (size_t)m.nrows);
-   dx.alloc((size_t)std::max(m.ncols, 1));
-   dx.zero();
-   HDA_HIP(hipMemcpyAsync(dx.data(), x, sizeof(double) * (size_t)m.nrows, hipMemcpyHostToDevice, Context::get().stream));
-   Context::get().sync();
-   PrecondFn M;
+   DArray<double> db = staged(b, m.nrows), dx = staged(x, m.nrows, m.ncols);
+   PrecondFn      M;
    if (amg) M = amg->pc.as_fn(m, nullptr);
    KrylovParams  k   = to_kparams(kp);
    LinOp         op(m, nullptr, (amg && amg->pc.amg) ? amg->pc.amg->vec_len0() : 0);
    KrylovResult  res = kind == 1 ? gmres(op, M, k, db.data(), dx.data()) : kind == 2 ? fgmres(op, M, k, db.data(), dx.data())
                      : kind == 3 ? bicgstab(op, M, k, db.data(), dx.data()) : pcg(op, M, k, db.data(), dx.data());
-   dx.download(x, (size_t)m.nrows);
+   fetch(dx.data(), x, m.nrows);
    if (hist)
       for (size_t i = 0; i < res.hist.size() && i < (size_t)k.max_iter + 1; i++) hist[i] = res.hist[i];
    if (iters) *iters = res.iters;
