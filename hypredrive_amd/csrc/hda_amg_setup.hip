@@ -1076,13 +1076,13 @@ __global__ __launch_bounds__(256) void k_interp_ub(int n, const int *__restrict_
                                                    const unsigned char *__restrict__ smask,
                                                    const int *__restrict__ cf, const int *__restrict__ nsC,
                                                    int *__restrict__ ub, int *__restrict__ hsz,
-                                                   int *__restrict__ cmark, int *__restrict__ nt)
+                                                   int *__restrict__ cmark)
 {
    const int i = blockIdx.x * 256 + threadIdx.x;
    if (i >= n) return;
    const int c = cf[i];
    cmark[i]    = (c == 1);
-   int u = 0, h = 0, t = 0;
+   int u = 0, h = 0;
    if (c == 1) u = 1;
    else if (c == -1)
    {
@@ -1092,13 +1092,12 @@ __global__ __launch_bounds__(256) void k_interp_ub(int n, const int *__restrict_
          const int j  = cj[k];
          const int cj_ = cf[j];
          if (cj_ == 1) u += 1;
-         else if (cj_ == -1) { u += nsC[j]; t += rp[j + 1] - rp[j]; }
+         else if (cj_ == -1) u += nsC[j];
       }
       h = u ? max(8, pow2ceil_dev(2 * u)) : 0;
    }
    ub[i]  = u;
    hsz[i] = h;
-   nt[i]  = t;
 }
 
 struct PEnt {
@@ -1410,9 +1409,16 @@ __global__ __launch_bounds__(256) void k_interp_build(
 // ballot bits in ascending kk, and within one neighbour row every target occurs once, so the
 // 64 lanes of a batch update distinct accumulators while batches and neighbours are visited
 // in order.  Rows that do not fit the LDS budget are flagged for k_interp_build.
-__host__ __device__ inline size_t interp_wave_doubles(int cap_row, int cap_ub, int cap_nbr)
-{ // doubles: rval[cap_row] Wv[cap_ub] nval[cap_nbr] misc[2]; ints: 6*cap_row + 2 + 4*cap_ub + cap_nbr
-   return (size_t)cap_row + cap_ub + cap_nbr + 2 + ((size_t)cap_row * 6 + 2 + (size_t)cap_ub * 4 + cap_nbr + 1) / 2 + 1;
+//
+// Neighbour-row staging area of a row group, in entries.  A row whose strong F neighbours hold at most this many entries together
+// copies them into LDS and works there; every other row reads its neighbour rows from memory, once each when they have at most four
+// entries a lane.  Larger areas lost on every level of the 256^3 hierarchy (level 1: 70 -> 59 ms, level 2: 36 -> 20 ms, levels 0 / 3:
+// 23.3 -> 22.2 / 5.0 -> 3.0 ms; docs/HISTORY.md round 3, profiles/r03_kernel_experiments.md): the small area lets more rows be in
+// flight per CU.
+constexpr int INTERP_NBR_CAP = 8;
+__host__ __device__ inline size_t interp_wave_doubles(int cap_row, int cap_ub)
+{ // doubles: rval[cap_row] Wv[cap_ub] nval[INTERP_NBR_CAP] misc[2]; ints: 6*cap_row + 2 + 4*cap_ub + INTERP_NBR_CAP
+   return (size_t)cap_row + cap_ub + INTERP_NBR_CAP + 2 + ((size_t)cap_row * 6 + 2 + (size_t)cap_ub * 4 + INTERP_NBR_CAP + 1) / 2 + 1;
 }
 #define WAVE_SYNC()                                         \
    do {                                                     \
@@ -1420,28 +1426,28 @@ __host__ __device__ inline size_t interp_wave_doubles(int cap_row, int cap_ub, i
       __builtin_amdgcn_wave_barrier();                      \
    } while (0)
 
-__global__ __launch_bounds__(256) void k_interp_rowmode(int n, const int *__restrict__ rp, const int *__restrict__ ub,
-                                                        const int *__restrict__ nt, int cap_row, int cap_ub, int cap_nbr,
+// rows for the thread kernel: the row or its candidate list exceeds the lane-group kernel's LDS areas (the length of the neighbour
+// rows does not matter: long ones are read from memory)
+__global__ __launch_bounds__(256) void k_interp_rowmode(int n, const int *__restrict__ rp, const int *__restrict__ ub, int cap_row, int cap_ub,
                                                         unsigned char *__restrict__ rowmode, int *__restrict__ hsz)
 {
    const int i = blockIdx.x * 256 + threadIdx.x;
    if (i >= n) return;
-   (void)nt; (void)cap_nbr; // long neighbour lists are read from global memory by the wave kernel
    const bool big = (rp[i + 1] - rp[i]) > cap_row || ub[i] > cap_ub;
    rowmode[i]     = big ? 1 : 0;
    if (!big) hsz[i] = 0; // no global hash table for rows the wave kernel handles
 }
-__global__ __launch_bounds__(256) void k_max3(int n, const int *__restrict__ rp, const int *__restrict__ ub, const int *__restrict__ nt, int *mx)
+// mx[0]: the longest row, mx[1]: the longest candidate list
+__global__ __launch_bounds__(256) void k_max2(int n, const int *__restrict__ rp, const int *__restrict__ ub, int *mx)
 {
-   int a = 0, b = 0, c = 0;
+   int a = 0, b = 0;
    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
    {
       a = max(a, rp[i + 1] - rp[i]);
       b = max(b, ub[i]);
-      c = max(c, nt[i]);
    }
-   for (int o = 32; o > 0; o >>= 1) { a = max(a, __shfl_xor(a, o)); b = max(b, __shfl_xor(b, o)); c = max(c, __shfl_xor(c, o)); }
-   if ((threadIdx.x & 63) == 0) { atomicMax(&mx[0], a); atomicMax(&mx[1], b); atomicMax(&mx[2], c); }
+   for (int o = 32; o > 0; o >>= 1) { a = max(a, __shfl_xor(a, o)); b = max(b, __shfl_xor(b, o)); }
+   if ((threadIdx.x & 63) == 0) { atomicMax(&mx[0], a); atomicMax(&mx[1], b); }
 }
 
 // value of lane l of the row's lane group.  With a whole wavefront per row l is wave-uniform (it comes out of a ballot), so the value
@@ -1463,10 +1469,9 @@ template <int G, bool PLUSI>
 __global__ __launch_bounds__(256, 5) void k_interp_wave(
    int n, const int *__restrict__ rp, const int *__restrict__ cj, const double *__restrict__ v,
    const unsigned char *__restrict__ smask, const unsigned char *__restrict__ sc, const int *__restrict__ cf, const int *__restrict__ nsC,
-   const long long *__restrict__ uofs, int cap_row, int cap_ub, int cap_nbr, int pmax, double trunc_factor,
+   const long long *__restrict__ uofs, int cap_row, int cap_ub, int pmax, double trunc_factor,
    const unsigned char *__restrict__ rowmode, int *__restrict__ lcol, double *__restrict__ lw, int *__restrict__ pcnt,
-   const int *__restrict__ dof, int s3_scan, unsigned long long *__restrict__ prof, int reg_nbr, const int *__restrict__ scofs,
-   const int *__restrict__ scc)
+   const int *__restrict__ dof, const int *__restrict__ scofs, const int *__restrict__ scc)
 {
    extern __shared__ double ilds[];
    constexpr int GPB = 256 / G;                    // row groups per workgroup
@@ -1474,14 +1479,14 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
    const int     gb  = (threadIdx.x & 63) & ~(G - 1); // first lane of the group inside its wavefront
    const unsigned long long gmask = ~0ULL >> (64 - G);
    auto gballot = [&](bool pr) -> unsigned long long { return (__ballot(pr) >> gb) & gmask; }; // votes of the group's lanes
-   const size_t per  = interp_wave_doubles(cap_row, cap_ub, cap_nbr);
-   double      *rval = ilds + grp * per, *Wv = rval + cap_row, *nval = Wv + cap_ub, *misc = nval + cap_nbr;
+   const size_t per  = interp_wave_doubles(cap_row, cap_ub);
+   double      *rval = ilds + grp * per, *Wv = rval + cap_row, *nval = Wv + cap_ub, *misc = nval + INTERP_NBR_CAP;
    int         *rcol = (int *)(misc + 2), *rofs = rcol + cap_row, *rtype = rofs + cap_row + 1; // rofs: cap_row + 1
    int         *noff = rtype + cap_row, *nbeg = noff + cap_row + 1;                         // neighbour-row staging: offsets, global starts
    double      *ksum = (double *)rcol; // per-neighbour sums of a staged row: over rcol and rofs, both dead by then
    int         *craw = nbeg + cap_row, *ucol = craw + cap_ub, *htb = ucol + cap_ub;         // htb: 2*cap_ub slots, col -> pos+1
-   int         *ncol = htb + 2 * cap_ub;                                                    // ncol: cap_nbr (bit 31 = strong C entry)
-   int         *sbeg = ncol + cap_nbr;                                                      // sbeg: cap_row, start of a strong-F neighbour's strong-C list
+   int         *ncol = htb + 2 * cap_ub;                                                    // ncol: INTERP_NBR_CAP (bit 31 = strong C entry)
+   int         *sbeg = ncol + INTERP_NBR_CAP;                                               // sbeg: cap_row, start of a strong-F neighbour's strong-C list
    const int    hmask = 2 * cap_ub - 1;
    auto lookup = [&](int m) -> int { // position of column m in C-hat_i or -1
       unsigned h = ((unsigned)m * 2654435761u) & (unsigned)hmask;
@@ -1495,16 +1500,6 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
    };
    const unsigned long long lt = (1ULL << lane) - 1; // the group's lanes below this one
    enum { T_DIAG = 0, T_SC = 1, T_SF = 2, T_OTHER = 3 };
-   // HDA_INTERP_PROF: shader-clock cycles per stage, summed over rows by every group's first lane (diagnostics)
-   unsigned long long tprev = 0;
-   auto stamp = [&](int st) {
-      if (prof)
-      {
-         const unsigned long long t = __builtin_readcyclecounter();
-         if (lane == 0 && st >= 0) atomicAdd(&prof[st], t - tprev);
-         tprev = t;
-      }
-   };
    // XCD-aware dealing of the rows (round 5): workgroups b, b + 8, ... share an XCD and its L2; they walk ONE contiguous eighth of the rows
    // instead of every eighth group of four.  A row reads the rows of its strong F neighbours -- the level-1 launch at 256^3 fetched 58 GB for
    // 2.2 GB of operator (profiles/r05f_setup_accounting.md) -- and rows that share neighbours (the same grid line, the next one) now meet in
@@ -1530,7 +1525,6 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
          if (lane == 0) pcnt[i] = 0;
          continue;
       }
-      stamp(-1);
       const int k0 = rp[i], nk = rp[i + 1] - k0;
       // ---- 1. stage the row, classify entries, candidate offsets per entry
       int running = 0;
@@ -1552,7 +1546,7 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
                cntk    = nsC[j];
                nbeg[k] = rp[j];
                noff[k] = rp[j + 1]; // (its end, until the scan of stage 1b turns it into an offset)
-               if (scc) sbeg[k] = scofs[j];
+               sbeg[k] = scofs[j];
             }
             rcol[k]  = j;
             rval[k]  = v[k0 + k];
@@ -1570,7 +1564,6 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
       }
       const int ncand = running;
       WAVE_SYNC();
-      stamp(0);
       // ---- 1b. stage the strong-F neighbour rows in LDS (one flat, fully parallel copy)
       int nrun = 0;
       for (int base = 0; base < nk; base += G)
@@ -1592,7 +1585,7 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
          nrun += __shfl(incl, G - 1, G);
       }
       const int  nbr_total = nrun;
-      const bool staged    = nbr_total <= cap_nbr; // otherwise neighbour rows are read from global memory
+      const bool staged    = nbr_total <= INTERP_NBR_CAP; // otherwise neighbour rows are read from global memory
       if (lane == 0) noff[nk] = nbr_total;
       WAVE_SYNC();
       if (staged)
@@ -1633,14 +1626,9 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
          }
       }
       WAVE_SYNC();
-      stamp(1);
-      // neighbour-row entry e of neighbour k (e relative to the row): column, value, strong-C flag
+      // neighbour-row entry e of neighbour k (e relative to the row): column, value
       auto nb_col = [&](int k, int e) -> int { return staged ? (ncol[noff[k] + e] & 0x7FFFFFFF) : cj[nbeg[k] + e]; };
       auto nb_val = [&](int k, int e) -> double { return staged ? nval[noff[k] + e] : v[nbeg[k] + e]; };
-      auto nb_sc  = [&](int k, int e) -> bool {
-         if (staged) return ncol[noff[k] + e] < 0;
-         return sc[nbeg[k] + e] != 0;
-      };
       // ---- 2. candidates in discovery order: entry k's candidates start at rofs[k]
       if (staged)
       { // one lane per row entry walks its staged neighbour row
@@ -1659,9 +1647,11 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
             }
          }
       }
-      else if (scc)
+      else
       { // one flat gather: candidate f belongs to the last row entry whose offset is <= f (entries without candidates share offsets);
-        // a strong C neighbour is its own candidate, a strong F neighbour contributes its list of strong C columns
+        // a strong C neighbour is its own candidate, a strong F neighbour contributes its list of strong C columns (scc).  Walking
+        // the strong F neighbours' full rows one after the other instead cost 54 against 47 ms on level 1 of the 256^3 hierarchy
+        // (profiles/r03_kernel_experiments.md).
          for (int f = lane; f < ncand; f += G)
          {
             int lo = 0, hi = nk - 1;
@@ -1674,86 +1664,11 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
             craw[f] = ((rtype[lo] & 7) == T_SC) ? rcol[lo] : scc[sbeg[lo] + (f - rofs[lo])];
          }
       }
-      else
-      for (int k = 0; k < nk; k++)
-      {
-         const int t = rtype[k] & 7;
-         if (t == T_SC) { if (lane == 0) craw[rofs[k]] = rcol[k]; }
-         else if (t == T_SF)
-         {
-            const int nj = noff[k + 1] - noff[k];
-            int       q = rofs[k];
-            for (int base = 0; base < nj; base += G)
-            {
-               const int kk = base + lane;
-               bool      f  = false;
-               int       m  = 0;
-               if (kk < nj)
-               {
-                  m = nb_col(k, kk);
-                  f = nb_sc(k, kk);
-               }
-               const unsigned long long b = gballot(f);
-               if (f) craw[q + __popcll(b & lt)] = m;
-               q += __popcll(b);
-            }
-         }
-      }
       WAVE_SYNC();
-      stamp(2);
-      // ---- 3. first occurrences -> C-hat_i in discovery order (ucol), accumulators to zero.
-      // A hash table over the candidates keeps, per column, the smallest candidate index (+1); a candidate is a
-      // first occurrence when that index is its own.
+      // ---- 3. first occurrences -> C-hat_i in discovery order (ucol), accumulators to zero: every lane scans the candidates before
+      // its own.  (An LDS hash table over the candidates was kept beside the scan for long lists until the setup clean-up; its
+      // threshold never left "always scan", and no measurement of it is on record.)
       int cnt = 0;
-      if (ncand <= s3_scan)
-      { // few candidates: every lane scans the ones before its own
-         for (int base = 0; base < ncand; base += G)
-         {
-            const int ci = base + lane;
-            bool      uq = false;
-            int       m  = 0;
-            if (ci < ncand)
-            {
-               m  = craw[ci];
-               uq = true;
-               for (int e = 0; e < ci; e++)
-                  if (craw[e] == m) { uq = false; break; }
-            }
-            const unsigned long long b = gballot(uq);
-            if (uq)
-            {
-               const int pos = cnt + __popcll(b & lt);
-               ucol[pos]     = m;
-               Wv[pos]       = 0.0;
-            }
-            cnt += __popcll(b);
-         }
-      }
-      else
-      {
-      for (int q = lane; q <= hmask; q += G) htb[q] = 0;
-      WAVE_SYNC();
-      for (int ci = lane; ci < ncand; ci += G)
-      {
-         const int m = craw[ci];
-         unsigned  h = ((unsigned)m * 2654435761u) & (unsigned)hmask;
-         for (;;)
-         {
-            int e = htb[h];
-            if (e == 0)
-            {
-               e = atomicCAS(&htb[h], 0, ci + 1);
-               if (e == 0) break;
-            }
-            if (craw[e - 1] == m) // the slot is this column's (its index only ever moves to an equal column)
-            {
-               atomicMin(&htb[h], ci + 1);
-               break;
-            }
-            h = (h + 1) & (unsigned)hmask;
-         }
-      }
-      WAVE_SYNC();
       for (int base = 0; base < ncand; base += G)
       {
          const int ci = base + lane;
@@ -1761,15 +1676,10 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
          int       m  = 0;
          if (ci < ncand)
          {
-            m          = craw[ci];
-            unsigned h = ((unsigned)m * 2654435761u) & (unsigned)hmask;
-            int      e = htb[h];
-            while (craw[e - 1] != m)
-            {
-               h = (h + 1) & (unsigned)hmask;
-               e = htb[h];
-            }
-            uq = (e == ci + 1);
+            m  = craw[ci];
+            uq = true;
+            for (int e = 0; e < ci; e++)
+               if (craw[e] == m) { uq = false; break; }
          }
          const unsigned long long b = gballot(uq);
          if (uq)
@@ -1780,8 +1690,8 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
          }
          cnt += __popcll(b);
       }
-      }
       WAVE_SYNC();
+      // the look-up table of C-hat_i: column -> position + 1
       for (int q = lane; q <= hmask; q += G) htb[q] = 0;
       WAVE_SYNC();
       for (int q = lane; q < cnt; q += G)
@@ -1790,7 +1700,6 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
          while (atomicCAS(&htb[h], 0, q + 1) != 0) h = (h + 1) & (unsigned)hmask;
       }
       WAVE_SYNC();
-      stamp(3);
       // ---- 4. weights, neighbours visited in ascending k
       if (lane == 0)
       {
@@ -1838,7 +1747,6 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
                ksum[k] = sum;
             }
          WAVE_SYNC();
-         stamp(4);
          // 4d. accumulation, neighbours in ascending k (the order every accumulator sees its terms in)
          for (int k = 0; k < nk; k++)
          {
@@ -1909,9 +1817,10 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
                continue;
             }
          }
-         if (reg_nbr && (t & 7) == T_SF && noff[k + 1] - noff[k] <= 4 * G)
+         if ((t & 7) == T_SF && noff[k + 1] - noff[k] <= 4 * G)
          { // the neighbour row fits four entries per lane: ONE pass over memory and one lookup per entry, the three sweeps below
-           // (a_jj, ordered sum, distribution) run on registers.  Same terms, same order as the general form that follows.
+           // (a_jj, ordered sum, distribution) run on registers.  Same terms, same order as the general form that follows, which
+           // keeps the longer neighbour rows.
             const int nj = noff[k + 1] - noff[k];
             int       mm[4], pp[4];
             double    aa[4];
@@ -2044,7 +1953,6 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
       if (diagonal != 0.0)
          for (int q = lane; q < cnt; q += G) Wv[q] = Wv[q] / (-diagonal);
       WAVE_SYNC();
-      stamp(staged ? 5 : 6);
       // ---- 5. truncation and output (serial parts on lane 0, exactly the oracle's sequence)
       const long long o = uofs[i];
       int             out_cnt = cnt;
@@ -2154,9 +2062,14 @@ __global__ __launch_bounds__(256, 5) void k_interp_wave(
          }
       }
       WAVE_SYNC();
-      stamp(7);
-      if (prof && lane == 0) atomicAdd(&prof[staged ? 8 : 9], 1ULL);
    }
+}
+
+// the instantiation for G lanes a row (8, 16 or a whole wavefront); all share one signature
+static auto interp_wave_kernel(int G, bool plus_i)
+{
+   if (plus_i) return G == 8 ? k_interp_wave<8, true> : G == 16 ? k_interp_wave<16, true> : k_interp_wave<64, true>;
+   return G == 8 ? k_interp_wave<8, false> : G == 16 ? k_interp_wave<16, false> : k_interp_wave<64, false>;
 }
 
 __global__ __launch_bounds__(256) void k_interp_gather(int n, const long long *__restrict__ uofs,
@@ -2232,50 +2145,33 @@ void amg_interp_extpi(const DCsr &A, const unsigned char *smask, const int *cf, 
    const int  itype  = (interp_type == 3 || interp_type == 8) ? interp_type : 6;
    const int n = A.nrows;
    const int g = ceil_div(std::max(n, 1), 256);
-   DArray<int>       nsC((size_t)n + 1), ub((size_t)n + 1), hsz((size_t)n + 1), cmark((size_t)n + 1), cidx((size_t)n + 1), nt((size_t)n + 1);
+   DArray<int>       nsC((size_t)n + 1), ub((size_t)n + 1), hsz((size_t)n + 1), cmark((size_t)n + 1), cidx((size_t)n + 1);
    DArray<long long> uofs((size_t)n + 1), hofs((size_t)n + 1);
    k_count_strongC<<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), smask, cf, nsC.data());
-   k_interp_ub<<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), smask, cf, nsC.data(), ub.data(), hsz.data(), cmark.data(), nt.data());
+   k_interp_ub<<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), smask, cf, nsC.data(), ub.data(), hsz.data(), cmark.data());
    HDA_TRACE("  interp: ub done");
    exclusive_scan(n, cmark.data(), cidx.data(), nullptr);
    // rows that fit the LDS budget go to the wave-per-row kernel, the rest keep the global-hash kernel
    DArray<unsigned char> rowmode((size_t)n + 1);
-   DArray<int>           mx(3);
+   DArray<int>           mx(2);
    mx.zero();
-   k_max3<<<std::min(g, 1024), 256, 0, STREAM>>>(n, A.rowptr.data(), ub.data(), nt.data(), mx.data());
-   int hmx[3] = {0, 0, 0};
-   mx.download(hmx, 3);
-   const char *imode = nullptr; // ("thread" / "wave" forced one kernel: diagnostics of rounds 1-3)
-   // G lanes share a row (8 for stencil rows, a whole wavefront for the long rows of coarse levels): the row, its
-   // candidates and its neighbour rows are staged in LDS by coalesced reads.  The thread-per-row kernel keeps the rows
-   // that exceed the LDS budget, and everything when pmax is outside the group kernel's range.
+   k_max2<<<std::min(g, 1024), 256, 0, STREAM>>>(n, A.rowptr.data(), ub.data(), mx.data());
+   int hmx[2] = {0, 0}; // the longest row, the longest candidate list
+   mx.download(hmx, 2);
+   // G lanes share a row (8 for stencil rows, a whole wavefront for the long rows of coarse levels): the row and its candidates
+   // are staged in LDS by coalesced reads.  The thread-per-row kernel keeps the rows that exceed the LDS budget, and everything
+   // when pmax is outside the group kernel's range.
    bool use_wave = pmax > 0 && pmax <= 16 && itype == 6; // the group kernel is extended+i only
-   if (imode && !strcmp(imode, "thread")) use_wave = false;
-   constexpr int g_env = 0;
    int G = 64; // (32 lanes for rows of ~30 entries measured twice as slow as 64: eight rows' staging areas leave one workgroup per CU)
    if (hmx[0] <= 8) G = 8;
    else if (hmx[0] <= 16) G = 16;
-   if (imode && !strcmp(imode, "wave")) G = 64;
-   if (g_env == 8 || g_env == 16 || g_env == 32 || g_env == 64) G = g_env;
-   const int gpb = 256 / G;
-   int cap_row = 8, cap_ub = 16, cap_nbr = 64;
-   cap_row = std::min(256, std::max(8, (hmx[0] + 7) / 8 * 8)); // rows longer than 256 entries keep the thread kernel
+   const int gpb     = 256 / G;
+   const int cap_row = std::min(256, std::max(8, (hmx[0] + 7) / 8 * 8)); // rows longer than 256 entries keep the thread kernel
+   int       cap_ub  = 16;
    while (cap_ub < hmx[1] && cap_ub < 1024) cap_ub <<= 1;
-   // Neighbour-row staging area per row group.  Since round 3 neighbour rows of up to four entries per lane are read ONCE from memory
-   // and swept on registers (reg_nbr below), which beat the LDS-staged form on every level of the 256^3 hierarchy (level 1: 70 -> 59 ms,
-   // level 2: 36 -> 20, levels 0 / 3: 23.3 -> 22.2 / 5.0 -> 3.0, tools/gpurun/r03_zg.sh ... r03_zi.sh) because the small area lets more
-   // rows be in flight per CU: the default area is 8 entries, i.e. staging is off in practice.  HDA_INTERP_NBR=<entries> brings it back.
-   constexpr int nbr_env = 0; // (the LDS staging of neighbour rows lost to the register sweeps on every level: closed in round 3)
-   cap_nbr = 8;
-   if (nbr_env > 8)
-   {
-      while (cap_nbr < hmx[2] && cap_nbr < nbr_env) cap_nbr <<= 1;
-      if (hmx[2] < cap_nbr) cap_nbr = std::max(8, (hmx[2] + 7) / 8 * 8); // every row's neighbourhood fits: no more than needed
-   }
-   while (cap_nbr > 64 && interp_wave_doubles(cap_row, cap_ub, cap_nbr) * 8 * gpb > 150 * 1024) cap_nbr >>= 1; // the workgroup's row groups must fit the LDS budget
-   if (interp_wave_doubles(cap_row, cap_ub, cap_nbr) * 8 * gpb > 150 * 1024) use_wave = false;
-   if (use_wave)
-      k_interp_rowmode<<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), ub.data(), nt.data(), cap_row, cap_ub, cap_nbr, rowmode.data(), hsz.data());
+   const size_t lds = interp_wave_doubles(cap_row, cap_ub) * 8 * gpb;
+   if (lds > 150 * 1024) use_wave = false; // the workgroup's row groups must fit the LDS budget
+   if (use_wave) k_interp_rowmode<<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), ub.data(), cap_row, cap_ub, rowmode.data(), hsz.data());
    exclusive_scan64(n, ub.data(), uofs.data());
    exclusive_scan64(n, hsz.data(), hofs.data());
    long long tot_u = 0, tot_h = 0;
@@ -2289,7 +2185,7 @@ void amg_interp_extpi(const DCsr &A, const unsigned char *smask, const int *cf, 
    if (tot_h) HDA_HIP(hipMemsetAsync(htab.data(), 0xFF, sizeof(int) * htab.size(), STREAM));
    DArray<int> pcnt((size_t)n + 1);
    pcnt.zero();
-   HDA_TRACE("  interp: build (tot_u=%lld tot_h=%lld nc=%d maxrow=%d maxub=%d maxnbr=%d lanes/row=%d caps %d %d %d)", tot_u, tot_h, nc, hmx[0], hmx[1], hmx[2], use_wave ? G : 1, cap_row, cap_ub, cap_nbr);
+   HDA_TRACE("  interp: build (tot_u=%lld tot_h=%lld nc=%d maxrow=%d maxub=%d lanes/row=%d caps %d %d)", tot_u, tot_h, nc, hmx[0], hmx[1], use_wave ? G : 1, cap_row, cap_ub);
    auto build_rows = [&](const unsigned char *mode) { // the thread-per-row kernel: on the rows flagged in mode, or on all of them
       auto kern = plus_i ? k_interp_build<true> : k_interp_build<false>;
       kern<<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), A.val.data(), smask, cf, uofs.data(), hofs.data(), lcol.data(), lw.data(),
@@ -2297,63 +2193,21 @@ void amg_interp_extpi(const DCsr &A, const unsigned char *smask, const int *cf, 
    };
    if (use_wave)
    {
-      const size_t lds = interp_wave_doubles(cap_row, cap_ub, cap_nbr) * 8 * gpb;
-      constexpr int s3_scan = 1 << 30; // candidates up to which duplicates are found by scanning
-      constexpr bool want_prof = false; // (shader-clock stage profile of rounds 2-3)
-      // neighbour rows read from memory, at most four entries per lane: one pass, the sweeps on registers (HDA_INTERP_REG=0: three passes)
-      constexpr int reg_nbr = 1;
-      DArray<unsigned long long> prof;
-      if (want_prof)
-      {
-         prof.alloc(10);
-         prof.zero();
-      }
       DArray<unsigned char> sc((size_t)std::max(A.nnz, 1));
       if (A.nnz) k_strongC_flag<<<std::min(ceil_div(A.nnz, 256), 1 << 16), 256, 0, STREAM>>>(A.nnz, A.col.data(), smask, cf, sc.data());
-      // compact lists of every row's strong C columns: a row gathers its candidates from them in one flat pass instead of walking the
-      // full rows of its strong F neighbours one after the other (HDA_INTERP_SCLIST=0: the walk)
-      constexpr bool sclist = true;
-      DArray<int> scofs, scc;
-      if (sclist && cap_nbr <= 8)
-      {
-         scofs.alloc((size_t)n + 1);
-         exclusive_scan(n, nsC.data(), scofs.data(), nullptr);
-         int tot_sc = 0;
-         HDA_HIP(hipMemcpyAsync(&tot_sc, scofs.data() + n, 4, hipMemcpyDeviceToHost, STREAM));
-         Context::get().sync();
-         scc.alloc((size_t)std::max(tot_sc, 1));
-         k_fill_strongC<<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), smask, cf, scofs.data(), scc.data());
-      }
-      auto launch = [&](auto kern) {
-         HDA_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-         kern<<<std::min((ceil_div(n, gpb) + 7) / 8 * 8, 256 * 16), 256, lds, STREAM>>>(n, A.rowptr.data(), A.col.data(), A.val.data(), smask, sc.data(), cf, nsC.data(),
-                                                                      uofs.data(), cap_row, cap_ub, cap_nbr, pmax, trunc_factor, rowmode.data(),
-                                                                      lcol.data(), lw.data(), pcnt.data(), dof, s3_scan, prof.data(), reg_nbr,
-                                                                      scc.data() ? scofs.data() : nullptr, scc.data());
-      };
-      if (plus_i)
-      {
-         if (G == 8) launch(k_interp_wave<8, true>);
-         else if (G == 16) launch(k_interp_wave<16, true>);
-         else if (G == 32) launch(k_interp_wave<32, true>);
-         else launch(k_interp_wave<64, true>);
-      }
-      else
-      {
-         if (G == 8) launch(k_interp_wave<8, false>);
-         else if (G == 16) launch(k_interp_wave<16, false>);
-         else if (G == 32) launch(k_interp_wave<32, false>);
-         else launch(k_interp_wave<64, false>);
-      }
-      if (want_prof)
-      {
-         unsigned long long h[10];
-         prof.download(h, 10);
-         const double rows = (double)std::max<unsigned long long>(h[8] + h[9], 1);
-         fprintf(stderr, "[hda] interp stages, cycles per row (%llu staged, %llu unstaged rows): row %.0f nbr-stage %.0f cand %.0f dedupe %.0f prep %.0f "
-                         "accumulate(staged) %.0f accumulate(unstaged) %.0f output %.0f\n", h[8], h[9], h[0] / rows, h[1] / rows, h[2] / rows,
-                 h[3] / rows, h[4] / rows, h[5] / rows, h[6] / rows, h[7] / rows);
-      }
+      // compact lists of every row's strong C columns: a row gathers its candidates from them in one flat pass
+      DArray<int> scofs((size_t)n + 1), scc;
+      exclusive_scan(n, nsC.data(), scofs.data(), nullptr);
+      int tot_sc = 0;
+      HDA_HIP(hipMemcpyAsync(&tot_sc, scofs.data() + n, 4, hipMemcpyDeviceToHost, STREAM));
+      Context::get().sync();
+      scc.alloc((size_t)std::max(tot_sc, 1));
+      k_fill_strongC<<<g, 256, 0, STREAM>>>(n, A.rowptr.data(), A.col.data(), smask, cf, scofs.data(), scc.data());
+      auto kern = interp_wave_kernel(G, plus_i);
+      HDA_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+      kern<<<std::min((ceil_div(n, gpb) + 7) / 8 * 8, 256 * 16), 256, lds, STREAM>>>(n, A.rowptr.data(), A.col.data(), A.val.data(), smask, sc.data(), cf, nsC.data(),
+                                                                                   uofs.data(), cap_row, cap_ub, pmax, trunc_factor, rowmode.data(), lcol.data(),
+                                                                                   lw.data(), pcnt.data(), dof, scofs.data(), scc.data());
       // the rows the wave kernel left to the thread kernel (rowmode): also when none of them needs a hash table
       // (C points and non-interpolated F points among them still have to report their entry count)
       build_rows(rowmode.data());
@@ -2767,11 +2621,9 @@ __global__ __launch_bounds__(NT) void k_spgemm_esc(int nchunks, const int *__res
 
 // cnt[row] currently holds (#heads in the chunk up to the row's end); turn it into the row's
 // own count using rowstart, which holds chunk_base + (#heads before the row)
-__global__ __launch_bounds__(256) void k_esc_fix_counts(int n, const int *__restrict__ xrp, const long long *__restrict__ eoff,
-                                                        const int *__restrict__ chunk_of_row_base_dummy, const long long *__restrict__ rowstart,
-                                                        const long long *__restrict__ chunkbase, int *__restrict__ cnt)
+__global__ __launch_bounds__(256) void k_esc_fix_counts(int n, const long long *__restrict__ rowstart, const long long *__restrict__ chunkbase,
+                                                        int *__restrict__ cnt)
 {
-   (void)xrp; (void)eoff; (void)chunk_of_row_base_dummy;
    const int i = blockIdx.x * 256 + threadIdx.x;
    if (i >= n) return;
    if (cnt[i] > 0) cnt[i] = (int)(chunkbase[i] + cnt[i] - rowstart[i]);
@@ -2807,16 +2659,8 @@ __global__ __launch_bounds__(256) void k_esc_compact(int n, const int *__restric
    }
 }
 
-static bool use_hash_spgemm()
-{
-   static int m = -1;
-   if (m < 0)
-   {
-      m = 0; // (the hash product stays the fallback for rows beyond the sort network and products beyond the scratch budget)
-   }
-   return m == 1;
-}
-
+// Expand-sort-compress in LDS; the hash product (spgemm_hash) is the fallback, for the reasons SetupRoute::why numbers: an empty
+// input, a row beyond the sort network, products beyond the scratch budget, a chunk beyond the key's row field.
 void spgemm(const DCsr &X, const DCsr &Y, DCsr &C)
 {
    HDA_REQUIRE(X.ncols <= Y.nrows || X.nnz == 0, "spgemm: inner dimensions");
@@ -2830,7 +2674,7 @@ void spgemm(const DCsr &X, const DCsr &Y, DCsr &C)
       route.why  = why;
       return spgemm_hash(X, Y, C);
    };
-   if (n == 0 || X.nnz == 0 || use_hash_spgemm()) return hash(1);
+   if (n == 0 || X.nnz == 0) return hash(1);
    DArray<int>       elen((size_t)X.nnz + 1), mx(1);
    DArray<long long> eoff((size_t)X.nnz + 1);
    k_entry_len<<<std::min(ceil_div(X.nnz, 256), 1 << 16), 256, 0, STREAM>>>(X.nnz, X.col.data(), Y.rowptr.data(), elen.data());
@@ -2871,9 +2715,8 @@ void spgemm(const DCsr &X, const DCsr &Y, DCsr &C)
    const size_t lds  = (size_t)cap * 16;
    // Eight keys per thread whatever the chunk capacity: a 4096 / 8192-product chunk gets 512 / 1024 threads, so that the two / one
    // workgroups a CU has LDS for still put 16 wavefronts on it (with 256 threads they left the CU at 8 / 4 and ran 1.5 - 3x slower per
-   // product, profiles/r03_kernel_experiments.md).  HDA_ESC_THREADS=256: the round-2 shape.
-   constexpr bool wide = true;
-   const int    nt   = wide ? cap / 8 : 256; // (four keys per thread -- twice the threads again -- lost 10-20 %: more cross-wave stages)
+   // product, profiles/r03_kernel_experiments.md).
+   const int    nt   = cap / 8; // (four keys per thread -- twice the threads again -- lost 10-20 %: more cross-wave stages)
    const int    grid = std::min(nchunks, 256 * std::max(1, (int)((160 * 1024) / (lds + 4 * nt + 1024)))); // the resident workgroups: no tail wave
 
    auto launch = [&](auto kern) {
@@ -2883,9 +2726,9 @@ void spgemm(const DCsr &X, const DCsr &Y, DCsr &C)
                                        mx.data());
    };
    if (cap == 2048) launch(k_spgemm_esc<8, 256>);
-   else if (cap == 4096) { if (wide) launch(k_spgemm_esc<8, 512>); else launch(k_spgemm_esc<16, 256>); }
-   else { if (wide) launch(k_spgemm_esc<8, 1024>); else launch(k_spgemm_esc<32, 256>); }
-   k_esc_fix_counts<<<ceil_div(n, 256), 256, 0, STREAM>>>(n, nullptr, nullptr, nullptr, rowstart.data(), chunkbase.data(), cnt.data());
+   else if (cap == 4096) launch(k_spgemm_esc<8, 512>);
+   else launch(k_spgemm_esc<8, 1024>);
+   k_esc_fix_counts<<<ceil_div(n, 256), 256, 0, STREAM>>>(n, rowstart.data(), chunkbase.data(), cnt.data());
    C.nrows = n;
    C.ncols = Y.ncols;
    C.rowptr.alloc((size_t)n + 1);

@@ -117,10 +117,8 @@ void permute_csr(DCsr &M, const int *perm, const int *col_rank, int nown)
          k_perm_copy<8><<<grid, 256, 0, STREAM>>>(n, perm, col_rank, nown, M.rowptr.data(), M.col.data(), M.val.data(), out.rowptr.data(),
                                                   out.col.data(), out.val.data());
    }
-   // Column-sorting the renamed rows again costs 50-80 ms of setup at 256^3 and buys 1.6 % of solve time
-   // (39.4 vs 40.0 ms): off unless asked for.  Nothing in the solve phase needs sorted rows.
-   constexpr bool resort = false;
-   if (col_rank && resort) sort_rows(out);
+   // The renamed rows are left unsorted: column-sorting them again costs 50-80 ms of setup at 256^3 and buys 1.6 % of solve time
+   // (39.4 vs 40.0 ms).  Nothing in the solve phase needs sorted rows.
    M = std::move(out);
    M.reset_plan();
 }
