@@ -130,6 +130,9 @@ def _signatures():
         "hda_csr_form": (I, [VP, I, IP]), "hda_spmv_mode": (I, [VP, I, I, D, D, DP, DP, DP, DP, DP, DP, DP, DP, DP, IP]),
         "hda_borrow_hypredrv": (I, [VP, OUT, OUT]), "hda_amd_partitioned_levels": (I, [VP]), "hda_amd_hierarchy_levels": (I, [VP]),
         "hda_halo_plan_host": (I, [I, LLP, LLP, I, IP, IP, IP, I, IP]),
+        "hda_dev_alloc": (I, [I64, OUT]), "hda_dev_free": (I, [VP]), "hda_dev_upload": (I, [VP, VP, I64]),
+        "hda_dev_download": (I, [VP, VP, I64]), "hda_borrow_ij_matrix": (I, [VP, OUT]), "hda_ij_ghost_gids": (I, [VP, LLP, I, IP]),
+        "hda_ij_last_assembly": (I, [DP]),
         "hda_probe_spmv": (I, [VP, I]), "hda_probe_read": (I, [DP, IP]), "hda_probe_add": (I, [VP, I, IP]),
         "hda_probe_read_id": (I, [I, DP, IP]),
         "hda_comm_stats": (I, [DP, I]), "hda_comm_name": (S, []), "hda_comm_size": (I, []), "hda_comm_selftest": (I, []),
@@ -980,6 +983,87 @@ def borrow_matrix(hypredrv_obj):
     a = C.c_void_p()
     _check(load().hda_borrow_hypredrv(hypredrv_obj.h, C.byref(a), None))
     return Csr(a, owned=True, keep=hypredrv_obj)
+
+
+class DeviceBuffer:
+    """A raw HBM buffer from the library's allocator (hda_dev_alloc): what a caller without torch hands to the IJ calls of an object
+    initialised with HYPRE_MEMORY_DEVICE.  .ptr is the device address, .nbytes its size; dtype and shape only describe the content."""
+
+    def __init__(self, nbytes, dtype=np.uint8, shape=None):
+        self.nbytes = int(nbytes)
+        self.dtype = np.dtype(dtype)
+        self.shape = (self.nbytes // self.dtype.itemsize,) if shape is None else tuple(shape)
+        p = C.c_void_p()
+        _check(load().hda_dev_alloc(self.nbytes, C.byref(p)))
+        self.ptr = p.value or 0
+
+    @staticmethod
+    def from_numpy(a, dtype=None):
+        a = np.ascontiguousarray(a, dtype=dtype)
+        b = DeviceBuffer(a.nbytes, a.dtype, a.shape)
+        _check(load().hda_dev_upload(b.ptr, a.ctypes.data, a.nbytes))
+        return b
+
+    @staticmethod
+    def empty(n, dtype=np.float64):
+        return DeviceBuffer(int(n) * np.dtype(dtype).itemsize, dtype, (int(n),))
+
+    def to_numpy(self):
+        out = np.empty(self.shape, dtype=self.dtype)
+        _check(load().hda_dev_download(out.ctypes.data, self.ptr, out.nbytes))
+        return out
+
+    def __len__(self):
+        return self.shape[0] if self.shape else 0
+
+    def __del__(self):
+        if getattr(self, "ptr", 0):
+            load().hda_dev_free(self.ptr)
+            self.ptr = 0
+
+
+def device_pointer(a):
+    """The device address behind a DeviceBuffer, an object with __cuda_array_interface__ (a torch tensor on the GPU) or data_ptr(); None
+    stays None (the NULL index array of the IJ vector calls)."""
+    if a is None:
+        return None
+    if isinstance(a, DeviceBuffer):
+        return a.ptr
+    if hasattr(a, "__cuda_array_interface__"):
+        return int(a.__cuda_array_interface__["data"][0])
+    if hasattr(a, "data_ptr"):
+        return int(a.data_ptr())
+    raise TypeError(f"not a device array: {type(a).__name__} (DeviceBuffer, __cuda_array_interface__ or data_ptr() expected)")
+
+
+def download_device(ptr, n, dtype=np.float64):
+    """n elements behind a raw device address as a numpy array"""
+    out = np.empty(int(n), dtype=dtype)
+    _check(load().hda_dev_download(out.ctypes.data, ptr, out.nbytes))
+    return out
+
+
+def borrow_ij(handle):
+    """Csr view of the operator behind an assembled HYPRE_IJMatrix handle (hypredrv.ij_matrix / ij_matrix_assemble): columns >= the
+    local column count are ghosts.  .ghost_gids: their ascending global ids.  Borrowed: keep the handle alive."""
+    A = _new_csr(load().hda_borrow_ij_matrix, handle, owned=True, keep=handle)  # destroying the view does not touch the operator
+    n = C.c_int()
+    _check(load().hda_ij_ghost_gids(handle, None, 0, C.byref(n)))
+    g = np.zeros(max(n.value, 1), dtype=np.int64)
+    _check(load().hda_ij_ghost_gids(handle, g.ctypes.data_as(C.POINTER(C.c_longlong)), n.value, C.byref(n)))
+    A.ghost_gids = g[:n.value]
+    return A
+
+
+IJ_PATHS = ("none", "csr", "sort")
+
+
+def ij_last_assembly():
+    """The last device-side HYPRE_IJMatrixAssemble of this rank: dict(path ("none", "csr": the stacked calls were a CSR block, "sort":
+    sort + run reduction), stacked, merged, sort_ms, reduce_ms)"""
+    v = (C.c_double * 5)()
+    _check(load().hda_ij_last_assembly(v))
+    return dict(path=IJ_PATHS[int(v[0])], stacked=int(v[1]), merged=int(v[2]), sort_ms=v[3], reduce_ms=v[4])
 
 
 def comm_stats(reset=False):

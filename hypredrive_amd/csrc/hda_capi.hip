@@ -1376,6 +1376,73 @@ extern "C" int hda_borrow_hypredrv(void *hypredrv, hda_csr_t *A, hda_amg_t *amg)
    HDA_CATCH
 }
 
+// Raw device buffers from the library's allocator: what a caller without a HIP client of its own (the Python binding's DeviceBuffer)
+// hands to the IJ calls of an object initialised with HYPRE_MEMORY_DEVICE.  Copies run on the library stream and are complete on return.
+extern "C" int hda_dev_alloc(int64_t bytes, void **ptr)
+{
+   HDA_TRY
+   HDA_REQUIRE(bytes >= 0 && ptr, "hda_dev_alloc: bytes >= 0 and ptr are required");
+   *ptr = pool_alloc((size_t)std::max<int64_t>(bytes, 1));
+   HDA_CATCH
+}
+extern "C" int hda_dev_free(void *ptr)
+{
+   if (!ptr) return HDA_OK;
+   HDA_TRY
+   Context::get().sync();
+   pool_free(ptr);
+   HDA_CATCH
+}
+extern "C" int hda_dev_upload(void *dst, const void *host, int64_t bytes)
+{
+   HDA_TRY
+   HDA_REQUIRE(bytes >= 0 && (bytes == 0 || (dst && host)), "hda_dev_upload: null buffer");
+   if (bytes) HDA_HIP(hipMemcpyAsync(dst, host, (size_t)bytes, hipMemcpyHostToDevice, Context::get().stream));
+   Context::get().sync();
+   HDA_CATCH
+}
+extern "C" int hda_dev_download(void *host, const void *src, int64_t bytes)
+{
+   HDA_TRY
+   HDA_REQUIRE(bytes >= 0 && (bytes == 0 || (src && host)), "hda_dev_download: null buffer");
+   download_sync(host, src, (size_t)bytes);
+   HDA_CATCH
+}
+
+// Borrowed view of the operator behind an assembled HYPRE_IJMatrix (columns >= its local column count are ghosts, in the order of
+// hda_ij_ghost_gids).  Valid until the handle is destroyed; release with hda_csr_destroy.
+extern "C" int hda_borrow_ij_matrix(void *ij_matrix, hda_csr_t *out)
+{
+   HDA_TRY
+   auto *m = (hypre_IJMatrix_struct *)ij_matrix;
+   HDA_REQUIRE(m && out && m->assembled, "hda_borrow_ij_matrix: an assembled IJ matrix is required");
+   auto v      = std::make_unique<hda_csr_s>();
+   v->borrowed = true;
+   v->ref      = &m->A;
+   *out        = v.release();
+   HDA_CATCH
+}
+// ascending global ids of its ghost columns: *n of them, the first min(*n, cap) written to gids (may be NULL with cap 0)
+extern "C" int hda_ij_ghost_gids(void *ij_matrix, long long *gids, int cap, int *n)
+{
+   auto *m = (hypre_IJMatrix_struct *)ij_matrix;
+   if (!m || !n) { g_err = "hda_ij_ghost_gids: null argument"; return HDA_ERR_ARG; }
+   *n = (int)m->ghost_gids.size();
+   for (int q = 0; q < *n && q < cap && gids; q++) gids[q] = m->ghost_gids[(size_t)q];
+   return HDA_OK;
+}
+
+// the last HYPRE_IJMatrixAssemble of an object initialised with HYPRE_MEMORY_DEVICE on this rank: out[0] path (0 nothing stacked, 1 the
+// stack was a CSR block, 2 sort + run reduction), [1] entries stacked, [2] entries after merging, [3] ms of the sort, [4] ms of the
+// run-reduce kernel (path 2; stream time)
+extern "C" int hda_ij_last_assembly(double out[5])
+{
+   if (!out) { g_err = "hda_ij_last_assembly: null argument"; return HDA_ERR_ARG; }
+   const IjAssemblyStats &s = ij_assembly_stats();
+   out[0] = s.path; out[1] = (double)s.stacked; out[2] = (double)s.merged; out[3] = s.sort_ms; out[4] = s.reduce_ms;
+   return HDA_OK;
+}
+
 // The library's halo-plan construction without its device half, for the CPU (gloo) test of the N > 1 path: collective over the
 // communicator joined with HYPREDRV_AMD_CommInitCallbacks.  part: row starts of every rank (world + 1 entries); ghost_gids:
 // ascending global ids of this rank's ghost columns.  Outputs: send_counts / recv_counts (world entries each), send_idx (the

@@ -12,6 +12,9 @@ struct hypre_IJVector_struct {
    long long            jlower = 0, jupper = -1;
    int                  nloc   = 0;
    bool                 initialized = false, assembled = false;
+   // what the last Initialize_v2 was given: where the CALLER's idx / value arrays of Set / AddTo / GetValues live (the vector's own
+   // data is HBM resident either way).  DEVICE: every call is applied to d at once (hda_ij_device.hip), stage stays empty
+   HYPRE_MemoryLocation location = HYPRE_MEMORY_HOST;
    std::vector<double>  stage;       // host values until Assemble
    hda::DArray<double>  d;           // owned entries (+ optional ghost room) in HBM
    size_t               capacity = 0; // doubles available behind data()
@@ -39,6 +42,20 @@ bool   known_zero_enabled();                        // HDA_KNOWN_ZERO (default o
 double vector_self_dot(hypre_IJVector_struct *v);   // <v,v>: cached per (vector, version) when the switch is on
 } // namespace hda
 
+namespace hda {
+// device-side stack of the (local row, global column, value, set / add) entries that HYPRE_IJMatrixSetValues / AddToValues were handed
+// through device pointers, in call order; grows by doubling
+struct IjStack {
+   DArray<int>           row;
+   DArray<long long>     col;
+   DArray<double>        val;
+   DArray<unsigned char> add;
+   size_t                size = 0;
+   void                  reserve(size_t need); // room for `need` entries, the first `size` kept
+   void                  clear();
+};
+} // namespace hda
+
 struct hypre_IJMatrix_struct {
    MPI_Comm  comm = MPI_COMM_WORLD;
    long long ilower = 0, iupper = -1, jlower = 0, jupper = -1;
@@ -49,6 +66,9 @@ struct hypre_IJMatrix_struct {
    std::vector<long long> t_col;
    std::vector<double>    t_val;
    std::vector<char>      t_add;
+   // what the last Initialize_v2 was given: where the caller's rows / cols / values arrays live.  DEVICE: the calls stack up in HBM
+   HYPRE_MemoryLocation   location = HYPRE_MEMORY_HOST;
+   hda::IjStack           stack;
    // assembled, HBM resident
    hda::DCsr              A;          // columns: [0,nloc) owned, >= nloc ghosts
    std::vector<long long> ghost_gids; // ascending global ids of the ghost columns
@@ -63,7 +83,33 @@ struct hypre_IJMatrix_struct {
    // a host CSR block with global column ids (HYPREDRV_LinearSystemSetMatrixFromCSR): uploaded as it is, columns mapped, rows sorted
    // and checked on the device; false = a row has a duplicate column (the staged path defines what that means)
    bool assemble_csr(const long long *indptr, const long long *cols, const double *data);
+   // the same for a block that is in HBM already: indptr (nloc + 1, any base), gcols / vals its nnz entries.  vals is adopted
+   bool assemble_csr_device(hda::DArray<long long> &indptr, hda::DArray<long long> &gcols, hda::DArray<double> &vals, long long nnz);
+   // pieces of the two above that the device IJ path (hda_ij_device.hip) shares: ghost_gids from nnz global columns in HBM; their local
+   // numbers (owned: c - jlower, ghosts: behind them in ghost_gids order); partition, halo plan and the assembled mark for a finished A
+   void collect_ghosts(const long long *gcols, long long nnz);
+   void map_columns(const long long *gcols, long long nnz, int *out) const;
+   void finish_assembly();
+   void assemble_device(); // from `stack`: bit for bit what assemble() builds from the same calls
 };
+namespace hda {
+// what the last assemble_device() of this rank did (test / measurement entry hda_ij_last_assembly): path 0 nothing stacked, 1 the
+// stack was a CSR block, 2 sort and run reduction; entries stacked and merged; stream time of the sort and of the run-reduce kernel
+struct IjAssemblyStats {
+   int       path = 0;
+   long long stacked = 0, merged = 0;
+   double    sort_ms = 0.0, reduce_ms = 0.0;
+};
+IjAssemblyStats &ij_assembly_stats();
+// HYPRE_IJMatrixSetValues / AddToValues with device pointers: false = a row outside the local range (the rows before it are stacked,
+// as the host path stacks them)
+bool ij_matrix_push_device(hypre_IJMatrix_struct *m, int nrows, const int *ncols, const long long *rows, const long long *cols,
+                           const double *vals, bool add);
+// HYPRE_IJVectorSetValues / AddToValues / GetValues with device pointers (idx may be NULL): false = an index outside the local range
+// (the entries before it are applied / returned)
+bool ij_vector_set_device(hypre_IJVector_struct *v, int n, const long long *idx, const double *val, bool add);
+bool ij_vector_get_device(hypre_IJVector_struct *v, int n, const long long *idx, double *out);
+} // namespace hda
 
 enum hda_solver_kind { HDA_SOLVER_PCG = 1, HDA_SOLVER_GMRES = 2, HDA_SOLVER_AMG = 3, HDA_SOLVER_ILU = 4, HDA_SOLVER_FGMRES = 5, HDA_SOLVER_BICGSTAB = 6, HDA_SOLVER_MGR = 7, HDA_SOLVER_SCHWARZ = 8, HDA_SOLVER_AMS = 9, HDA_SOLVER_FSAI = 10 };
 

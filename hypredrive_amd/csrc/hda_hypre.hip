@@ -140,10 +140,20 @@ extern "C" HYPRE_Int HYPRE_IJVectorDestroy(HYPRE_IJVector v)
    return 0;
 }
 extern "C" HYPRE_Int HYPRE_IJVectorSetObjectType(HYPRE_IJVector, HYPRE_Int) { return 0; }
-extern "C" HYPRE_Int HYPRE_IJVectorInitialize_v2(HYPRE_IJVector v, HYPRE_MemoryLocation)
+extern "C" HYPRE_Int HYPRE_IJVectorInitialize_v2(HYPRE_IJVector v, HYPRE_MemoryLocation loc)
 {
    HY_TRY
-   v->stage.assign((size_t)v->nloc, 0.0);
+   v->location = loc == HYPRE_MEMORY_DEVICE ? HYPRE_MEMORY_DEVICE : HYPRE_MEMORY_HOST;
+   if (v->location == HYPRE_MEMORY_DEVICE)
+   { // the values live in HBM from the start: zero there (on a machine without a device the first Set / Get call is the one refused)
+      std::vector<double>().swap(v->stage);
+      if (have_device())
+      {
+         v->ensure_device();
+         if (v->nloc) HDA_HIP(hipMemsetAsync(v->data(), 0, sizeof(double) * (size_t)v->nloc, STREAM));
+      }
+   }
+   else v->stage.assign((size_t)v->nloc, 0.0);
    v->touch();
    v->initialized = true;
    v->assembled   = false;
@@ -153,6 +163,15 @@ extern "C" HYPRE_Int HYPRE_IJVectorInitialize(HYPRE_IJVector v) { return HYPRE_I
 
 static HYPRE_Int vec_set(HYPRE_IJVector v, HYPRE_Int n, const HYPRE_BigInt *idx, const HYPRE_Complex *val, bool add)
 {
+   if (v->location == HYPRE_MEMORY_DEVICE)
+   { // idx (or NULL) and val are device pointers: applied to the HBM storage at once, in call order (hda_ij_device.hip)
+      HY_NEED_DEVICE;
+      HY_TRY
+      const bool ok = ij_vector_set_device(v, n, idx, val, add);
+      v->assembled  = false;
+      if (!ok) return hypre_set_error(HYPRE_ERROR_ARG, "IJVector index outside the local range");
+      HY_CATCH
+   }
    HY_TRY
    if (!v->initialized) HYPRE_IJVectorInitialize(v);
    if (v->assembled && v->stage.empty())
@@ -196,6 +215,13 @@ extern "C" HYPRE_Int HYPRE_IJVectorAssemble(HYPRE_IJVector v)
 }
 extern "C" HYPRE_Int HYPRE_IJVectorGetValues(HYPRE_IJVector v, HYPRE_Int n, const HYPRE_BigInt *idx, HYPRE_Complex *val)
 {
+   if (v->location == HYPRE_MEMORY_DEVICE)
+   { // idx (or NULL) and val are device pointers
+      HY_NEED_DEVICE;
+      HY_TRY
+      if (!ij_vector_get_device(v, n, idx, val)) return hypre_set_error(HYPRE_ERROR_ARG, "IJVector index outside the local range");
+      HY_CATCH
+   }
    HY_TRY
    std::vector<double> h;
    const double       *src;
@@ -417,8 +443,9 @@ extern "C" HYPRE_Int HYPRE_IJMatrixSetRowSizes(HYPRE_IJMatrix m, const HYPRE_Int
    HY_CATCH
 }
 extern "C" HYPRE_Int HYPRE_IJMatrixSetDiagOffdSizes(HYPRE_IJMatrix, const HYPRE_Int *, const HYPRE_Int *) { return 0; }
-extern "C" HYPRE_Int HYPRE_IJMatrixInitialize_v2(HYPRE_IJMatrix m, HYPRE_MemoryLocation)
+extern "C" HYPRE_Int HYPRE_IJMatrixInitialize_v2(HYPRE_IJMatrix m, HYPRE_MemoryLocation loc)
 {
+   m->location    = loc == HYPRE_MEMORY_DEVICE ? HYPRE_MEMORY_DEVICE : HYPRE_MEMORY_HOST;
    m->initialized = true;
    m->assembled   = false;
    return 0;
@@ -428,6 +455,15 @@ extern "C" HYPRE_Int HYPRE_IJMatrixInitialize(HYPRE_IJMatrix m) { return HYPRE_I
 static HYPRE_Int mat_set(HYPRE_IJMatrix m, HYPRE_Int nrows, HYPRE_Int *ncols, const HYPRE_BigInt *rows,
                          const HYPRE_BigInt *cols, const HYPRE_Complex *values, bool add)
 {
+   if (m->location == HYPRE_MEMORY_DEVICE)
+   { // all four arrays are device pointers: the call goes onto the device-side stack (hda_ij_device.hip)
+      HY_NEED_DEVICE;
+      HY_TRY
+      const bool ok = ij_matrix_push_device(m, nrows, ncols, rows, cols, values, add);
+      if (!ok) return hypre_set_error(HYPRE_ERROR_ARG, "IJMatrix row outside the local range (off-rank assembly is not supported)");
+      if (nrows > 0) m->assembled = false;
+      HY_CATCH
+   }
    HY_TRY
    size_t q = 0;
    for (int r = 0; r < nrows; r++)
@@ -608,7 +644,6 @@ bool hypre_IJMatrix_struct::assemble_csr(const long long *indptr, const long lon
    const long long nnz = indptr[nloc] - indptr[0];
    DArray<long long> dip, dgc;
    DArray<double>    dv;
-   DArray<int>       drp((size_t)nloc + 1);
    dip.upload(indptr, (size_t)nloc + 1);
    if (nnz)
    {
@@ -620,29 +655,54 @@ bool hypre_IJMatrix_struct::assemble_csr(const long long *indptr, const long lon
       dgc.alloc(1);
       dv.alloc(1);
    }
+   return assemble_csr_device(dip, dgc, dv, nnz);
+}
+
+bool hypre_IJMatrix_struct::assemble_csr_device(DArray<long long> &dip, DArray<long long> &dgc, DArray<double> &dv, long long nnz)
+{
+   DArray<int> drp((size_t)nloc + 1);
    k_indptr_to_rowptr<<<ceil_div(nloc + 1, 256), 256, 0, STREAM>>>(nloc, dip.data(), drp.data());
-   // ghost columns: the few entries that leave [jlower, jupper] are collected on the device, sorted and made unique on the host
-   ghost_gids.clear();
-   if (nnz)
-   {
-      DArray<unsigned long long> cnt(1);
-      cnt.zero();
-      const int g = std::min(ceil_div(nnz, 256), 1 << 16);
-      k_ghost_cols<<<g, 256, 0, STREAM>>>((long)nnz, dgc.data(), jlower, jupper, cnt.data(), nullptr);
-      unsigned long long ng = 0;
-      cnt.download(&ng, 1);
-      if (ng)
-      {
-         DArray<long long> out((size_t)ng);
-         cnt.zero();
-         k_ghost_cols<<<g, 256, 0, STREAM>>>((long)nnz, dgc.data(), jlower, jupper, cnt.data(), out.data());
-         std::vector<long long> gh = out.to_host();
-         std::sort(gh.begin(), gh.end());
-         gh.erase(std::unique(gh.begin(), gh.end()), gh.end());
-         ghost_gids = gh;
-      }
-   }
+   collect_ghosts(dgc.data(), nnz);
    return adopt_device(nloc, (int)nnz, drp, dgc, dv, true);
+}
+
+// ghost columns: the few entries that leave [jlower, jupper] are collected on the device, sorted and made unique on the host
+void hypre_IJMatrix_struct::collect_ghosts(const long long *gcols, long long nnz)
+{
+   ghost_gids.clear();
+   if (!nnz) return;
+   DArray<unsigned long long> cnt(1);
+   cnt.zero();
+   const int g = std::min(ceil_div(nnz, 256), 1 << 16);
+   k_ghost_cols<<<g, 256, 0, STREAM>>>((long)nnz, gcols, jlower, jupper, cnt.data(), nullptr);
+   unsigned long long ng = 0;
+   cnt.download(&ng, 1);
+   if (ng)
+   {
+      DArray<long long> out((size_t)ng);
+      cnt.zero();
+      k_ghost_cols<<<g, 256, 0, STREAM>>>((long)nnz, gcols, jlower, jupper, cnt.data(), out.data());
+      std::vector<long long> gh = out.to_host();
+      std::sort(gh.begin(), gh.end());
+      gh.erase(std::unique(gh.begin(), gh.end()), gh.end());
+      ghost_gids = gh;
+   }
+}
+
+void hypre_IJMatrix_struct::map_columns(const long long *gcols, long long nnz, int *out) const
+{
+   if (!nnz) return;
+   DArray<long long> dgh;
+   if (!ghost_gids.empty()) dgh.upload(ghost_gids.data(), ghost_gids.size());
+   k_map_gcols<<<std::min(ceil_div(nnz, 256), 1 << 16), 256, 0, STREAM>>>((long)nnz, gcols, jlower, jupper, (int)(jupper - jlower + 1), dgh.data(),
+                                                                         (int)ghost_gids.size(), out);
+}
+
+void hypre_IJMatrix_struct::finish_assembly()
+{
+   Context::get().sync();
+   finish_partition(this);
+   assembled = true;
 }
 
 bool hypre_IJMatrix_struct::adopt_device(int nl, int nnz, DArray<int> &rowptr, DArray<long long> &gcols, DArray<double> &vals, bool refuse_duplicates)
@@ -686,6 +746,15 @@ extern "C" HYPRE_Int HYPRE_IJMatrixAssemble(HYPRE_IJMatrix m)
    HY_NEED_DEVICE;
    HY_TRY
    set_stage("matrix assembly (HYPRE_IJMatrixAssemble)");
+   if (m->location == HYPRE_MEMORY_DEVICE)
+   { // the calls since Initialize_v2(DEVICE) are on the device-side stack
+      HDA_REQUIRE(m->t_row.empty(), "an IJMatrix initialised with HYPRE_MEMORY_DEVICE still holds values set through host pointers");
+      if (m->assembled && m->stack.size == 0) return 0;
+      HDA_REQUIRE(!m->assembled, "re-assembly of an assembled IJMatrix with new values is not supported");
+      m->assemble_device();
+      return 0;
+   }
+   HDA_REQUIRE(m->stack.size == 0, "an IJMatrix initialised with HYPRE_MEMORY_HOST still holds values set through device pointers");
    if (m->assembled && m->t_row.empty()) return 0;
    HDA_REQUIRE(!m->assembled || m->t_row.empty(), "re-assembly of an assembled IJMatrix with new values is not supported");
    m->assemble();

@@ -1591,6 +1591,17 @@ extern "C" uint32_t HYPREDRV_AMD_ProbeDominant(HYPREDRV_t h, int arm, int *level
    }
    API_CATCH
 }
+// read-only HBM view of a vector's owned entries (cdata(): the version counter stays where it is)
+extern "C" uint32_t HYPREDRV_AMD_IJVectorDevicePointer(HYPRE_IJVector vec, const double **ptr, HYPRE_Int *n)
+{
+   if (!vec || !ptr || !n) return err_set(ERR_UNKNOWN_HYPREDRV_OBJ);
+   API_TRY
+   HDA_REQUIRE(vec->stage.empty(), "HYPREDRV_AMD_IJVectorDevicePointer: the vector holds host values that were not assembled");
+   vec->ensure_device();
+   *ptr = vec->cdata();
+   *n   = vec->nloc;
+   API_CATCH
+}
 extern "C" uint32_t HYPREDRV_LinearSystemComputeEigenspectrum(HYPREDRV_t h) { CHECK_INIT_OBJ(h); return g_err; } // no-op unless built with eigspec
 
 // ------------------------------------------------------------- THE HOT PATH

@@ -141,6 +141,123 @@ def ij_vector(values, jlower=0):
     return h
 
 
+MEMORY_HOST, MEMORY_DEVICE = 0, 1  # HYPRE_MemoryLocation
+
+
+def hypre_error_text():
+    """the text of the last failed HYPRE_* call of this rank (HYPRE_DescribeError), cleared with the error flag"""
+    L = lib()
+    buf = C.create_string_buffer(128)
+    L.HYPRE_DescribeError.argtypes = [C.c_int, C.c_char_p]
+    L.HYPRE_DescribeError(L.HYPRE_GetError(), buf)
+    L.HYPRE_ClearAllErrors()
+    return buf.value.decode(errors="replace")
+
+
+def _ij_check(code, what):
+    if code:
+        raise LibraryError(f"{what} failed: {hypre_error_text()}")
+
+
+def _ij_device_sigs(L):
+    vp = C.c_void_p
+    L.HYPRE_IJMatrixCreate.argtypes = [C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, C.POINTER(vp)]
+    L.HYPRE_IJMatrixSetObjectType.argtypes = L.HYPRE_IJVectorSetObjectType.argtypes = [vp, C.c_int]
+    L.HYPRE_IJMatrixInitialize_v2.argtypes = L.HYPRE_IJVectorInitialize_v2.argtypes = [vp, C.c_int]
+    L.HYPRE_IJMatrixAssemble.argtypes = L.HYPRE_IJMatrixDestroy.argtypes = [vp]
+    L.HYPRE_IJVectorAssemble.argtypes = L.HYPRE_IJVectorDestroy.argtypes = [vp]
+    L.HYPRE_IJMatrixSetValues.argtypes = L.HYPRE_IJMatrixAddToValues.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    L.HYPRE_IJVectorCreate.argtypes = [C.c_int, C.c_longlong, C.c_longlong, C.POINTER(vp)]
+    L.HYPRE_IJVectorSetValues.argtypes = L.HYPRE_IJVectorAddToValues.argtypes = L.HYPRE_IJVectorGetValues.argtypes = [vp, C.c_int, vp, vp]
+    L.HYPREDRV_AMD_IJVectorDevicePointer.argtypes = [vp, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int)]
+    L.HYPREDRV_AMD_IJVectorDevicePointer.restype = C.c_uint32
+
+
+def _count(a):
+    """elements of a device array argument (DeviceBuffer, torch tensor, __cuda_array_interface__)"""
+    if hasattr(a, "__cuda_array_interface__"):
+        return int(np.prod(a.__cuda_array_interface__["shape"], dtype=np.int64))
+    if hasattr(a, "numel"):
+        return int(a.numel())
+    return len(a)
+
+
+def ij_matrix_device(ncols, rows, cols, vals, ilower, iupper, jlower, jupper, add=False, handle=None):
+    """One HYPRE_IJMatrixSetValues (add: AddToValues) call with DEVICE arrays -- int32 ncols and int64 rows (one per row of the call),
+    int64 cols and float64 vals (one per entry); DeviceBuffers, torch-ROCm tensors or anything with __cuda_array_interface__ /
+    data_ptr(), passed without a copy -- on a matrix initialised with HYPRE_MEMORY_DEVICE.  handle=None creates that matrix for rows
+    [ilower, iupper] and columns [jlower, jupper]; handle= stacks a further call on an open one.  Returns the handle, not assembled
+    (ij_matrix_assemble).  A pointer of the wrong kind is undefined behaviour, as in hypre."""
+    from ._lib import device_pointer
+    L = lib()
+    _ij_device_sigs(L)
+    if handle is None:
+        handle = C.c_void_p()
+        _ij_check(L.HYPRE_IJMatrixCreate(MPI_COMM_WORLD, ilower, iupper, jlower, jupper, C.byref(handle)), "HYPRE_IJMatrixCreate")
+        L.HYPRE_IJMatrixSetObjectType(handle, 5555)
+        _ij_check(L.HYPRE_IJMatrixInitialize_v2(handle, MEMORY_DEVICE), "HYPRE_IJMatrixInitialize_v2")
+    fn = L.HYPRE_IJMatrixAddToValues if add else L.HYPRE_IJMatrixSetValues
+    _ij_check(fn(handle, _count(ncols), device_pointer(ncols), device_pointer(rows), device_pointer(cols), device_pointer(vals)),
+              "HYPRE_IJMatrixAddToValues" if add else "HYPRE_IJMatrixSetValues")
+    return handle
+
+
+def ij_matrix_assemble(handle):
+    """HYPRE_IJMatrixAssemble: the operator is built on the device from the stacked calls; returns the handle"""
+    L = lib()
+    _ij_device_sigs(L)
+    _ij_check(L.HYPRE_IJMatrixAssemble(handle), "HYPRE_IJMatrixAssemble")
+    return handle
+
+
+def ij_vector_device(values, jlower, idx=None, add=False, handle=None, n=None):
+    """One HYPRE_IJVectorSetValues (add: AddToValues) call with DEVICE arrays: float64 values, int64 idx (None: entries jlower, jlower
+    + 1, ...).  handle=None creates a vector of len(values) entries starting at jlower (n: another length), initialised with
+    HYPRE_MEMORY_DEVICE; handle= applies a further call.  Returns the handle, assembled."""
+    from ._lib import device_pointer
+    L = lib()
+    _ij_device_sigs(L)
+    cnt = _count(values)
+    if handle is None:
+        handle = C.c_void_p()
+        nloc = cnt if n is None else int(n)
+        _ij_check(L.HYPRE_IJVectorCreate(MPI_COMM_WORLD, jlower, jlower + nloc - 1, C.byref(handle)), "HYPRE_IJVectorCreate")
+        L.HYPRE_IJVectorSetObjectType(handle, 5555)
+        _ij_check(L.HYPRE_IJVectorInitialize_v2(handle, MEMORY_DEVICE), "HYPRE_IJVectorInitialize_v2")
+    fn = L.HYPRE_IJVectorAddToValues if add else L.HYPRE_IJVectorSetValues
+    _ij_check(fn(handle, cnt, device_pointer(idx), device_pointer(values)), "HYPRE_IJVectorAddToValues" if add else "HYPRE_IJVectorSetValues")
+    _ij_check(L.HYPRE_IJVectorAssemble(handle), "HYPRE_IJVectorAssemble")
+    return handle
+
+
+def ij_vector_get_device(handle, idx=None, n=None):
+    """HYPRE_IJVectorGetValues of a vector initialised with HYPRE_MEMORY_DEVICE into a new DeviceBuffer: the entries idx names (a
+    device int64 array), or the first n owned ones (idx=None; n=None: all of them)."""
+    from ._lib import DeviceBuffer, device_pointer
+    L = lib()
+    _ij_device_sigs(L)
+    if idx is None and n is None:
+        ll = C.POINTER(C.c_longlong)
+        L.HYPRE_IJVectorGetLocalRange.argtypes = [C.c_void_p, ll, ll]
+        lo, hi = C.c_longlong(), C.c_longlong()
+        L.HYPRE_IJVectorGetLocalRange(handle, C.byref(lo), C.byref(hi))
+        n = hi.value - lo.value + 1
+    cnt = _count(idx) if idx is not None else int(n)
+    out = DeviceBuffer.empty(cnt, np.float64)
+    _ij_check(L.HYPRE_IJVectorGetValues(handle, cnt, device_pointer(idx), out.ptr), "HYPRE_IJVectorGetValues")
+    return out
+
+
+def vector_device_view(handle):
+    """(device address, n) of the owned entries of an IJ vector handle -- HYPREDRV_AMD_IJVectorDevicePointer: read-only, valid until the
+    vector is next modified or destroyed.  _lib.download_device(ptr, n) copies it to the host."""
+    L = lib()
+    _ij_device_sigs(L)
+    p, n = C.POINTER(C.c_double)(), C.c_int()
+    check(L.HYPREDRV_AMD_IJVectorDevicePointer(handle, C.byref(p), C.byref(n)))
+    return C.cast(p, C.c_void_p).value or 0, n.value
+
+
 class HypredrvError(LibraryError):
     def __init__(self, code, msg):
         super().__init__(f"HYPREDRV error 0x{code:08x}: {msg}")
@@ -258,6 +375,14 @@ class Hypredrv:
         check(lib().HYPREDRV_LinearSystemGetSolutionValues(self.h, C.byref(p)))
         check(lib().HYPREDRV_LinearSystemGetSolutionLength(self.h, C.byref(n)))
         return np.ctypeslib.as_array(p, shape=(max(n.value, 1),))[:n.value].copy()
+
+    def solution_handle(self):
+        """the solution as an IJ vector handle (HYPREDRV_LinearSystemGetSolution); vector_device_view(handle) reads it in HBM"""
+        v = C.c_void_p()
+        lib().HYPREDRV_LinearSystemGetSolution.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        lib().HYPREDRV_LinearSystemGetSolution.restype = C.c_uint32
+        check(lib().HYPREDRV_LinearSystemGetSolution(self.h, C.byref(v)))
+        return v
 
     def solution_norm(self, kind="L2"):
         v = C.c_double()

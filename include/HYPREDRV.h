@@ -173,6 +173,9 @@ HYPREDRV_EXPORT_SYMBOL uint32_t HYPREDRV_AMD_LastResidualNorms(HYPREDRV_t hypred
  * plain-CSR operator with HIP events (returns its level and local rows/cols/nnz); arm == 0 returns the
  * average launch duration and disarms */
 HYPREDRV_EXPORT_SYMBOL uint32_t HYPREDRV_AMD_ProbeDominant(HYPREDRV_t hypredrv, int arm, int *level, double dims[3], double *avg_ms, int *count);
+/* Read-only HBM view of the owned entries of an IJ vector (*n of them), valid until the vector is next modified or destroyed: the
+ * solution of HYPREDRV_LinearSystemGetSolution without the host mirror.  Does not count as a modification of the vector. */
+HYPREDRV_EXPORT_SYMBOL uint32_t HYPREDRV_AMD_IJVectorDevicePointer(HYPRE_IJVector vec, const double **ptr, HYPRE_Int *n);
 
 #ifdef __cplusplus
 }

@@ -386,6 +386,21 @@ int hda_probe_read_id(int id, double *avg_ms, int *count);
  * measurement entries above run on the very objects HYPREDRV_LinearSolverSetup built.  Valid until
  * HYPREDRV_LinearSolverDestroy; release the views with hda_csr_destroy / hda_amg_destroy. */
 int hda_borrow_hypredrv(void *hypredrv, hda_csr_t *A, hda_amg_t *amg);
+/* Raw device buffers from the library's allocator, for callers that hand DEVICE pointers to the IJ calls (include/HYPRE.h: objects
+ * initialised with HYPRE_MEMORY_DEVICE) and have no HIP client of their own.  Copies are complete when the call returns. */
+int hda_dev_alloc(int64_t bytes, void **ptr);
+int hda_dev_free(void *ptr);
+int hda_dev_upload(void *dst, const void *host, int64_t bytes);
+int hda_dev_download(void *host, const void *src, int64_t bytes);
+/* Borrowed view of the operator behind an assembled HYPRE_IJMatrix: columns >= the local column count are ghosts, in the order of the
+ * ascending global ids hda_ij_ghost_gids returns (*n of them; the first min(*n, cap) are written).  Valid until the handle is
+ * destroyed; release the view with hda_csr_destroy. */
+int hda_borrow_ij_matrix(void *ij_matrix, hda_csr_t *A);
+int hda_ij_ghost_gids(void *ij_matrix, long long *gids, int cap, int *n);
+/* The last HYPRE_IJMatrixAssemble of a matrix initialised with HYPRE_MEMORY_DEVICE: out[0] path (0 nothing stacked, 1 the stacked calls
+ * were a CSR block, 2 sort + run reduction), [1] entries stacked, [2] entries after merging, [3] / [4] stream milliseconds of the sort
+ * and of the run-reduce kernel (path 2). */
+int hda_ij_last_assembly(double out[5]);
 /* Host half of the library's halo plan (who owns every ghost column, what every peer wants from this rank), collective over
  * the communicator joined with HYPREDRV_AMD_CommInitCallbacks; touches no device, so the world_size-2/3 gloo tests drive the
  * library's own partition code on CPU.  part: world + 1 row starts; ghost_gids ascending. */

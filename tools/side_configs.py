@@ -19,7 +19,10 @@ iteration count == oracle's.  bench.py carries them as budgeted extras; `python 
                   dominant kernel's bytes / time (`python tools/side_configs.py ams 64`)
   fsai N          not a BASELINE config: PCG + static FSAI (the preconditioner block of examples/ex1-fsai-static.yml) on
                   the N^3 7-point Laplacian: iterations, ms per solve, setup seconds, nnz(G) / n, and the application's bytes / time
-                  beside the l1-Jacobi sweep on the same A (`python tools/side_configs.py fsai 128`)"""
+                  beside the l1-Jacobi sweep on the same A (`python tools/side_configs.py fsai 128`)
+  assemble N      not a BASELINE config: the N^3 7-point Laplacian assembled four ways -- host IJ calls, SetMatrixFromCSR, device pointers
+                  in CSR order, device pointers as shuffled finite-element-style adds: ms of each, and the sort and
+                  run-reduce kernels of the last on their own (`python tools/side_configs.py assemble 128`)"""
 import json
 import os
 import sys
@@ -283,10 +286,109 @@ def pcg_fsai(hh, n=128, steps=3, warmup=1, reps=20):
     return out
 
 
+def assemble(hh, n=128, reps=5, warmup=1, ways="abcd"):
+    """The n^3 7-point Laplacian built four ways, each warmed up and timed `reps` times in this process (median; every timing ends
+    with the operator assembled and the stream drained):
+      (a) host IJ: HYPRE_IJMatrixSetValues with host pointers, all rows in order in one call, + Assemble (what a row-at-a-time driver
+          makes the library do per entry; the call overhead of one call per row is not in it)
+      (b) HYPREDRV_LinearSystemSetMatrixFromCSR: host arrays, CSR-direct
+      (c) device pointers, CSR-ordered, set-only: SetValues + Assemble (the arrays are in HBM before the clock starts)
+      (d) device pointers, every entry split into 2 - 8 AddToValues contributions and the whole list shuffled (finite-element style),
+          one call + Assemble; the sort and the run-reduce kernel also on their own, with bytes / time against the bytes they must move:
+          sort = key (8) + position (4) in and out; reduce = 21 B per stacked entry in, 12 B per merged entry out"""
+    import ctypes as C
+    from hypredrive_amd import DeviceBuffer, _lib
+    from hypredrive_amd import hypredrv as hd
+    L = hd.lib()
+    M = hh.lap7(n, n, n, want_rhs=False).to_scipy()
+    N, nnz = M.shape[0], M.nnz
+    ip, ix, v = M.indptr.astype(np.int64), M.indices.astype(np.int64), np.ascontiguousarray(M.data)
+    ncols, rows = np.diff(ip).astype(np.int32), np.arange(N, dtype=np.int64)
+    rng = np.random.default_rng(1)
+    k = rng.integers(2, 9, nnz)
+    T = int(k.sum())
+    src = np.repeat(np.arange(nnz), k)
+    q = rng.permutation(T)
+    src = src[q]
+    d_rows, d_cols = np.repeat(rows, ncols)[src], ix[src]
+    d_vals = (v / k)[src]
+    del q, src
+    dev = {name: DeviceBuffer.from_numpy(a) for name, a in dict(ncols=ncols, rows=rows, cols=ix, vals=v, one=np.ones(T, dtype=np.int32), drows=d_rows,
+                                                                 dcols=d_cols, dvals=d_vals).items()}
+    del d_rows, d_cols, d_vals
+    keep = {}
+
+    def host_ij():
+        hd._ij_device_sigs(L)
+        m = C.c_void_p()
+        L.HYPRE_IJMatrixCreate(hd.MPI_COMM_WORLD, 0, N - 1, 0, N - 1, C.byref(m))
+        L.HYPRE_IJMatrixInitialize_v2(m, hd.MEMORY_HOST)
+        assert L.HYPRE_IJMatrixSetValues(m, N, ncols.ctypes.data, rows.ctypes.data, ix.ctypes.data, v.ctypes.data) == 0
+        assert L.HYPRE_IJMatrixAssemble(m) == 0
+        return m
+
+    def from_csr():
+        h = hd.Hypredrv("solver: pcg\npreconditioner: amg\n")
+        h.set_matrix_csr(0, N - 1, ip, ix, v)
+        return h
+
+    def device_csr():
+        return hd.ij_matrix_assemble(hd.ij_matrix_device(dev["ncols"], dev["rows"], dev["cols"], dev["vals"], 0, N - 1, 0, N - 1))
+
+    def device_adds():
+        m = hd.ij_matrix_assemble(hd.ij_matrix_device(dev["one"], dev["drows"], dev["dcols"], dev["dvals"], 0, N - 1, 0, N - 1, add=True))
+        keep.setdefault("stats", []).append(_lib.ij_last_assembly())
+        return m
+
+    def drop(obj):
+        if hasattr(obj, "close"):
+            obj.close()
+        else:
+            L.HYPRE_IJMatrixDestroy(obj)
+
+    out = {"what": f"assembly of the {n}^3 7-point Laplacian four ways; median of {reps} after {warmup} warm-up, same process",
+           "rows": N, "entries": nnz, "stacked_entries_d": T}
+    for name, fn in (("a_host_ij", host_ij), ("b_from_csr", from_csr), ("c_device_csr", device_csr), ("d_device_adds", device_adds)):
+        if name[0] not in ways:  # (a kernel trace of (d) alone: `assemble N d`)
+            continue
+        ts = []
+        for rep in range(warmup + reps):
+            hh.sync()
+            t0 = time.perf_counter()
+            obj = fn()
+            hh.sync()
+            ts.append((time.perf_counter() - t0) * 1e3)
+            if name == "c_device_csr" and rep == 0:
+                S = _lib.borrow_ij(obj).to_scipy()
+                out["c_equals_generator"] = bool(np.array_equal(S.indptr, M.indptr) and np.array_equal(S.indices, M.indices) and np.array_equal(S.data, M.data))
+                out["c_path"] = _lib.ij_last_assembly()["path"]
+            if name == "d_device_adds" and rep == 0:
+                S = _lib.borrow_ij(obj).to_scipy()
+                out["d_pattern_equals_generator"] = bool(np.array_equal(S.indptr, M.indptr) and np.array_equal(S.indices, M.indices))
+                out["d_max_rel_diff"] = float(np.max(np.abs(S.data - M.data) / np.abs(M.data)))
+            drop(obj)
+        ts = ts[warmup:]
+        out[name + "_ms"] = float(np.median(ts))
+        out[name + "_ms_all"] = [round(t, 3) for t in ts]
+    if "d" not in ways:
+        return out
+    st = keep["stats"][warmup:]
+    sort_ms, red_ms = float(np.median([s["sort_ms"] for s in st])), float(np.median([s["reduce_ms"] for s in st]))
+    sort_by, red_by = 2.0 * 12.0 * T, 21.0 * T + 12.0 * st[0]["merged"]
+    out["d_path"] = st[0]["path"]
+    out["d_sort"] = {"kernel": "rocprim::radix_sort_pairs, 64-bit key + 32-bit position", "bytes": sort_by, "avg_ms": sort_ms,
+                     "gbs": sort_by / sort_ms / 1e6 if sort_ms else None, "frac": sort_by / sort_ms / 1e6 / HBM_PEAK_GBS if sort_ms else None}
+    out["d_reduce"] = {"kernel": "k_ij_reduce_runs", "bytes": red_by, "avg_ms": red_ms, "gbs": red_by / red_ms / 1e6 if red_ms else None,
+                       "frac": red_by / red_ms / 1e6 / HBM_PEAK_GBS if red_ms else None}
+    return out
+
+
 if __name__ == "__main__":
     import hypredrive_amd as hh
     which = sys.argv[1] if len(sys.argv) > 1 else "mgr"
-    if which == "schwarz":
+    if which == "assemble":
+        print(json.dumps(assemble(hh, int(sys.argv[2]) if len(sys.argv) > 2 else 128, ways=sys.argv[3] if len(sys.argv) > 3 else "abcd")))
+    elif which == "schwarz":
         print(json.dumps(gmres_schwarz(hh, int(sys.argv[2]) if len(sys.argv) > 2 else 128)))
     elif which == "ams":
         print(json.dumps(pcg_ams(hh, int(sys.argv[2]) if len(sys.argv) > 2 else 64)))
