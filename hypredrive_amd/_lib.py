@@ -124,6 +124,9 @@ def _signatures():
         "hda_amg_fold_sweep": (I, [VP, I, DP, DP, DP, DP, DP]), "hda_amg_blocks": (I, [VP]), "hda_amg_level_blocks": (I, [VP, I, LP]),
         "hda_amg_complexities": (I, [VP, DP, DP]), "hda_amg_vcycle_bytes": (D, [VP]), "hda_amg_vcycle": (I, [VP, DP, DP]),
         "hda_pcg": krylov, "hda_gmres": krylov, "hda_fgmres": krylov, "hda_bicgstab": krylov,
+        "hda_spmm": (I, [VP, I, I, D, D, DP, DP, DP, DP, DP, DP, DP]), "hda_multi_blas": (I, [I, I, I, DP, DP, IP, DP, DP, DP, DP, DP]),
+        "hda_amg_vcycle_multi": (I, [VP, I, DP, DP]), "hda_pcg_multi": (I, [VP, VP, KRY, I, DP, DP, DP, IP, IP, DP]),
+        "hda_time_kernel_multi": (I, [I, VP, VP, I, I, DP, DP]),
         "hda_time_kernel": (I, [I, VP, VP, I, DP, DP]), "hda_set_overlap": (None, [I]), "hda_last_precond_calls": (I, []),
         "hda_solve_device": (I, [VP, VP, KRY, I, DP, I, DP, IP, DP, DP, DP, DP]),
         "hda_pcg_iteration_bytes": (D, [VP]), "hda_format_bytes": (I, [VP, VP, DP, DP, DP, IP]),
@@ -225,6 +228,12 @@ def _blocks_or(blocks, block_part):
     return (blocks, None) if block_part is None else _blocks(block_part)
 
 
+def _cols(a):
+    """a multivector as a 2-d float64 array, one column per vector (a 1-d array is one column)"""
+    a = np.asarray(a, dtype=np.float64)
+    return a.reshape(-1, 1) if a.ndim == 1 else a
+
+
 def _new_csr(fn, *args, **how):
     """call an entry whose last argument is the new matrix handle; how: owned=False, keep=... for a borrowed view"""
     out = C.c_void_p()
@@ -297,6 +306,22 @@ class Csr:
         y = np.zeros(self.nrows) if y is None else np.ascontiguousarray(y, dtype=np.float64).copy()
         _check(load().hda_spmv(self.h, alpha, _dp(x), beta, _dp(y)))
         return y
+
+    def spmm(self, X, mode="plain", alpha=1.0, beta=0.0, Yin=None, B=None, dinv=None, W=None, Y=None):
+        """One batched product on k <= 8 columns (X: ncols x k; Yin, B, W: nrows x k; dinv: nrows), a SPMM_MODES name: plain Y = alpha
+        A X + beta Yin, resid Y = B - A X, jacobi Y = X + dinv * (B - A X).  Y: what the output starts from (rows the product does
+        not write come back unchanged).  Returns (Y, dots): Y nrows x k, dots the k values <W_j, Y_j> or None without W."""
+        X = _cols(X)
+        k = X.shape[1]
+        n = self.nrows
+        Yin, B, W = (None if v is None else _cols(v) for v in (Yin, B, W))
+        out = np.zeros((k, n)) if Y is None else np.ascontiguousarray(np.asarray(Y, dtype=np.float64).T).copy()
+        dots = np.zeros(max(k, 1))
+        p = lambda v: None if v is None else _dp(np.ascontiguousarray(v.T))
+        dv = None if dinv is None else np.ascontiguousarray(dinv, dtype=np.float64)
+        _check(load().hda_spmm(self.h, SPMM_MODES[mode], k, alpha, beta, p(X), p(Yin), p(B), None if dv is None else _dp(dv), p(W), _dp(out),
+                               _dp(dots) if W is not None else None))
+        return out.T.copy(), (dots[:k].copy() if W is not None else None)
 
     def relax(self, b, x, relax_type=18, weight=1.0, sweeps=1):
         b = np.ascontiguousarray(b, dtype=np.float64)
@@ -554,6 +579,15 @@ class Amg:
         x = np.zeros_like(b)
         _check(load().hda_amg_vcycle(self.h, _dp(b), _dp(x)))
         return x
+
+    def vcycle_multi(self, B):
+        """One V-cycle from a zero guess on the k <= 8 columns of B (n x k) in one pass over every operator; returns X (n x k)."""
+        B = _cols(B)
+        k = B.shape[1]
+        bt = np.ascontiguousarray(B.T)
+        xt = np.zeros_like(bt)
+        _check(load().hda_amg_vcycle_multi(self.h, k, _dp(bt), _dp(xt)))
+        return xt.T.copy()
 
 
 MGR_INTERP = {"injection": 0, "l1-jacobi": 1, "jacobi": 2, "blk-jacobi": 12}
@@ -868,6 +902,53 @@ def fgmres(A, b, amg=None, kp=None, x0=None):
 
 def bicgstab(A, b, amg=None, kp=None, x0=None):
     return _krylov(load().hda_bicgstab, A, b, amg, kp or KrylovParams.default(False), x0)
+
+
+def pcg_multi(A, B, amg=None, kp=None, X0=None):
+    """k <= 8 PCG solves in lockstep, one per column of B (n x k; X0: the initial guesses, zero by default).  Returns a list of the
+    dicts pcg returns, one per column."""
+    kp = kp or KrylovParams.default(False)
+    B = _cols(B)
+    n, k = B.shape
+    bt = np.ascontiguousarray(B.T)
+    xt = np.zeros_like(bt) if X0 is None else np.ascontiguousarray(_cols(X0).T).copy()
+    hist = np.zeros((max(k, 1), kp.max_iter + 1))
+    it, conv, frel = np.zeros(max(k, 1), dtype=np.int32), np.zeros(max(k, 1), dtype=np.int32), np.zeros(max(k, 1))
+    _check(load().hda_pcg_multi(A.h, amg.h if amg is not None else None, C.byref(kp), k, _dp(bt), _dp(xt), _dp(hist), _ip(it), _ip(conv), _dp(frel)))
+    return [dict(x=xt[j].copy(), iters=int(it[j]), converged=bool(conv[j]), final_rel=float(frel[j]), hist=hist[j, :it[j] + 1].copy())
+            for j in range(k)]
+
+
+MBLAS_OPS = {"dot": 0, "update": 1, "dir": 2}
+SPMM_MODES = {"plain": 0, "resid": 1, "jacobi": 2}
+
+
+def multi_blas(op, U, V=None, P=None, S=None, alpha=None, beta=None, active=None):
+    """The batched BLAS-1 of the PCG recurrences on the k <= 8 columns of n x k arrays (an MBLAS_OPS name).  dot: the k values <U_j,
+    V_j>.  update: (U + alpha_j P, V - alpha_j S, the k values <V_j, V_j> afterwards).  dir: P + beta_j U.  A column whose active
+    flag is 0 gets alpha_j = beta_j = 0."""
+    U = _cols(U)
+    n, k = U.shape
+    t = lambda v: None if v is None else np.ascontiguousarray(_cols(v).T).copy()
+    ut, vt, pt, st = t(U), t(V), t(P), t(S)
+    p = lambda v: None if v is None else _dp(v)
+    f = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float64)
+    al, be = f(alpha), f(beta)
+    ac = None if active is None else np.ascontiguousarray(active, dtype=np.int32)
+    out = np.zeros(max(k, 1))
+    _check(load().hda_multi_blas(MBLAS_OPS[op], k, n, p(al), p(be), None if ac is None else _ip(ac), p(pt), p(st), p(ut), p(vt), _dp(out)))
+    if op == "dot":
+        return out[:k].copy()
+    if op == "update":
+        return ut.T.copy(), vt.T.copy(), out[:k].copy()
+    return ut.T.copy()
+
+
+def time_kernel_multi(kind, A, k, amg=None, reps=20):
+    """time_kernel for the batched kernels on k columns: kind 0 product, 1 Jacobi sweep, 2 residual, 3 one batched V-cycle"""
+    ms, by = C.c_double(), C.c_double()
+    _check(load().hda_time_kernel_multi(kind, A.h, amg.h if amg is not None else None, k, reps, C.byref(ms), C.byref(by)))
+    return ms.value, by.value
 
 
 def time_kernel(kind, A, amg=None, reps=20):

@@ -404,6 +404,13 @@ class Amg {
    double *first_sweep_dest(double *x); // where apply(b, x) puts its zero-guess first sweep: x or the level's second buffer
    // general solve entry: max_iter cycles starting from the x passed in
    void solve(const double *b, double *x);
+   // one V-cycle from a zero guess on K = 2, 4 or 8 interleaved vectors (hda_multi.hip): the cycle of cycle()
+   // written straight on the plain CSR arrays -- Jacobi-family sweeps, R as the level stores it, dense coarsest solve, P -- without
+   // the single-vector fusions.  What it does not run is refused by name here, never at setup (multi_cycle_refusal; empty = runs).
+   // Work vectors of width K per level are made at the first call and live with the object.
+   void        apply_multi(const double *B, double *X, int K);
+   std::string multi_cycle_refusal() const;
+   double      vcycle_multi_bytes(int K) const; // algorithmic HBM bytes of that cycle (spmm_bytes per product)
 
    int           num_levels() const { return (int)levels.size(); }
    const DCsr   &level_A(int l) const { return l == 0 ? *A0 : levels[l].A; }
@@ -459,6 +466,10 @@ class Amg {
    DArray<double>        coarse_invT; // dense inverse of the coarsest operator (column-major)
    int                   coarse_n = 0;
    bool                  coarse_dense = false;
+   // apply_multi: right-hand side, iterate, second iterate buffer and residual of every level, rows x multi_K_ (level 0: u2 and t only)
+   struct MultiWork { DArray<double> f, u, u2, t; };
+   std::vector<MultiWork> multi_work_;
+   int                    multi_K_ = 0;
 };
 
 // ---- AMS (hda_ams.hip): auxiliary-space Maxwell preconditioner on one rank.  Parameter contract: reference AMS_args

@@ -2,6 +2,7 @@
 #include "../../include/hypredrv_amd.h"
 
 #include "hda_precond.h"
+#include "hda_multi.h"
 #include "hda_comm.h"
 #include "hda_hypre.h"
 
@@ -1154,6 +1155,190 @@ extern "C" int hda_bicgstab(hda_csr_t A, hda_amg_t amg, const hda_krylov_params 
                             double *hist, int *iters, int *converged, double *final_rel)
 {
    return run_krylov(3, A, amg, kp, b, x, hist, iters, converged, final_rel);
+}
+
+// ------------------------------------------------- up to 8 right-hand sides at once
+
+static int multi_width_checked(int k)
+{
+   const std::string why = multi_refusal(k);
+   if (!why.empty()) throw Error(why);
+   return multi_width(k);
+}
+// k host vectors of n (vector j at host + j * n; k * n values are read) interleaved over K columns: max(n, 1) * K elements, padding zero
+static DArray<double> staged_multi(const double *host, int k, int n, int K)
+{
+   DArray<double> cm = staged(host, k * n), d((size_t)std::max(n, 1) * K);
+   if (n == 0) d.zero();
+   multi_pack(n, k, K, cm.data(), n, d.data());
+   return d;
+}
+// ... and the k columns of n x K interleaved results back: exactly k * n values
+static void fetch_multi(const double *dev, double *host, int k, int n, int K)
+{
+   DArray<double> cm = room<double>(k * n);
+   multi_unpack(n, k, K, dev, cm.data(), n);
+   fetch(cm.data(), host, k * n);
+}
+// the first k entries of a scalar block
+static void fetch_block(int block, double *host, int k)
+{
+   fetch(MultiScratch::get().block(block), host, k);
+}
+
+extern "C" int hda_spmm(hda_csr_t A, int mode, int k, double alpha, double beta, const double *X, const double *Yin, const double *B, const double *dinv,
+                        const double *W, double *Y, double *dots)
+{
+   HDA_TRY
+   const DCsr &m = A->get();
+   const int   K = multi_width_checked(k);
+   HDA_REQUIRE(X && Y, "hda_spmm: X and Y are required");
+   HDA_REQUIRE(mode == HDA_SPMM_PLAIN || mode == HDA_SPMM_RESID || mode == HDA_SPMM_JACOBI, "hda_spmm: unknown mode");
+   HDA_REQUIRE(mode != HDA_SPMM_PLAIN || beta == 0.0 || Yin, "hda_spmm: beta != 0 needs Yin");
+   HDA_REQUIRE(mode == HDA_SPMM_PLAIN || B, "hda_spmm: the residual and the Jacobi sweep need B");
+   HDA_REQUIRE(mode != HDA_SPMM_JACOBI || (dinv && m.nrows <= m.ncols), "hda_spmm: the Jacobi sweep needs dinv and reads x[i] of every row (ncols >= nrows)");
+   HDA_REQUIRE(!W || dots, "hda_spmm: W needs dots");
+   // X: k x ncols; Yin, B, W, Y: k x nrows; dinv: nrows
+   DArray<double> dX = staged_multi(X, k, m.ncols, K), dY = staged_multi(Y, k, m.nrows, K), dYin, dB, dW, dd;
+   if (Yin && mode == HDA_SPMM_PLAIN) dYin = staged_multi(Yin, k, m.nrows, K);
+   if (B && mode != HDA_SPMM_PLAIN) dB = staged_multi(B, k, m.nrows, K);
+   if (W) dW = staged_multi(W, k, m.nrows, K);
+   if (mode == HDA_SPMM_JACOBI) dd = staged(dinv, m.nrows);
+   spmm(m, K, mode, alpha, dX.data(), beta, dYin.data(), dB.data(), dd.data(), W ? dW.data() : nullptr, dY.data(), W ? MS_TMP : -1);
+   if (W)
+   {
+      if (m.nrows > 0)
+      {
+         multi_finalize(K, MS_TMP, 1, MV_TMP);
+         fetch_block(MV_TMP, dots, k);
+      }
+      else
+         for (int j = 0; j < k; j++) dots[j] = 0.0;
+   }
+   fetch_multi(dY.data(), Y, k, m.nrows, K);
+   HDA_CATCH
+}
+
+extern "C" int hda_multi_blas(int op, int k, int n, const double *alpha, const double *beta, const int *active, const double *P, const double *S,
+                              double *U, double *V, double *out)
+{
+   HDA_TRY
+   const int K = multi_width_checked(k);
+   HDA_REQUIRE(n >= 0 && U, "hda_multi_blas: n >= 0 and U are required");
+   // alpha, beta, active, out: k entries; P, S, U, V: k x n
+   int flags[kMultiMax];
+   for (int j = 0; j < kMultiMax; j++) flags[j] = j < k && (!active || active[j]);
+   multi_set_active(flags);
+   DArray<double> dU = staged_multi(U, k, n, K);
+   if (op == HDA_MBLAS_DOT)
+   {
+      HDA_REQUIRE(V && out, "hda_multi_blas: the dot products need V and out");
+      DArray<double> dV = staged_multi(V, k, n, K);
+      multi_dot(n, K, dU.data(), dV.data(), MS_TMP);
+      multi_finalize(K, MS_TMP, 1, MV_TMP);
+      fetch_block(MV_TMP, out, k);
+   }
+   else if (op == HDA_MBLAS_UPDATE)
+   {
+      HDA_REQUIRE(alpha && P && S && V && out, "hda_multi_blas: the update needs alpha, P, S, V and out");
+      DArray<double> dV = staged_multi(V, k, n, K), dP = staged_multi(P, k, n, K), dS = staged_multi(S, k, n, K), da = staged(alpha, k, kMultiMax);
+      multi_masked(K, da.data(), MV_ALPHA);
+      multi_cg_update(n, K, MultiScratch::get().block(MV_ALPHA), dP.data(), dS.data(), dU.data(), dV.data(), MS_RR);
+      multi_finalize(K, MS_RR, 1, MV_TMP);
+      fetch_block(MV_TMP, out, k);
+      fetch_multi(dU.data(), U, k, n, K);
+      fetch_multi(dV.data(), V, k, n, K);
+   }
+   else if (op == HDA_MBLAS_DIR)
+   {
+      HDA_REQUIRE(beta && P, "hda_multi_blas: the direction step needs beta and P");
+      DArray<double> dP = staged_multi(P, k, n, K), db = staged(beta, k, kMultiMax);
+      multi_masked(K, db.data(), MV_BETA);
+      multi_cg_dir(n, K, MultiScratch::get().block(MV_BETA), dP.data(), dU.data());
+      fetch_multi(dU.data(), U, k, n, K);
+   }
+   else throw Error("hda_multi_blas: unknown op");
+   HDA_CATCH
+}
+
+extern "C" int hda_amg_vcycle_multi(hda_amg_t h, int k, const double *B, double *X)
+{
+   HDA_TRY
+   HDA_REQUIRE(h && h->pc.amg, "hda_amg_vcycle_multi: the handle is not a BoomerAMG hierarchy");
+   HDA_REQUIRE(B && X, "hda_amg_vcycle_multi: B and X are required");
+   const int      K = multi_width_checked(k);
+   const DCsr    &m = h->pc.amg->level_A(0);
+   DArray<double> dB = staged_multi(B, k, m.nrows, K), dX = room<double>(std::max(m.nrows, 1) * K); // B, X: k x n
+   h->pc.amg->apply_multi(dB.data(), dX.data(), K);
+   fetch_multi(dX.data(), X, k, m.nrows, K);
+   HDA_CATCH
+}
+
+extern "C" int hda_pcg_multi(hda_csr_t A, hda_amg_t amg, const hda_krylov_params *kp, int k, const double *B, double *X, double *hist, int *iters,
+                             int *converged, double *final_rel)
+{
+   HDA_TRY
+   const DCsr &m = A->get();
+   const int   K = multi_width_checked(k);
+   HDA_REQUIRE(B && X, "hda_pcg_multi: B and X are required");
+   HDA_REQUIRE(!amg || amg->pc.amg, "hda_pcg_multi: the preconditioner must be a BoomerAMG hierarchy or NULL");
+   KrylovParams   kk = to_kparams(kp);
+   DArray<double> dB = staged_multi(B, k, m.nrows, K), dX = staged_multi(X, k, m.nrows, K); // B, X: k x n
+   const std::vector<KrylovResult> res = pcg_multi(m, amg ? amg->pc.amg : nullptr, kk, k, dB.data(), dX.data());
+   fetch_multi(dX.data(), X, k, m.nrows, K);
+   for (int j = 0; j < k; j++)
+   { // hist: k x (max_iter + 1); iters, converged, final_rel: k
+      const KrylovResult &r = res[(size_t)j];
+      if (hist)
+         for (size_t i = 0; i < r.hist.size() && i < (size_t)kk.max_iter + 1; i++) hist[(size_t)j * ((size_t)kk.max_iter + 1) + i] = r.hist[i];
+      if (iters) iters[j] = r.iters;
+      if (converged) converged[j] = r.converged ? 1 : 0;
+      if (final_rel) final_rel[j] = r.final_rel;
+   }
+   HDA_CATCH
+}
+
+extern "C" int hda_time_kernel_multi(int kind, hda_csr_t A, hda_amg_t amg, int k, int reps, double *avg_ms, double *bytes)
+{
+   HDA_TRY
+   Context       &ctx = Context::get();
+   const DCsr    &m   = A->get();
+   const int      K   = multi_width_checked(k);
+   const size_t   nv  = (size_t)std::max(std::max(m.ncols, m.nrows), 1);
+   DArray<double> x(nv * K), y(nv * K), b(nv * K), dinv(nv);
+   fill((int)(nv * K), 1.0, x.data());
+   fill((int)(nv * K), 0.5, b.data());
+   {
+      DArray<double> d((size_t)std::max(m.nrows, 1));
+      l1_row_norms(m, 1, d.data());
+      make_dinv(m.nrows, d.data(), 1.0, dinv.data());
+   }
+   HDA_REQUIRE(kind != 3 || (amg && amg->pc.amg), "batched V-cycle timing needs a hierarchy");
+   auto launch = [&]() {
+      switch (kind)
+      {
+         case 0: spmm(m, K, MM_PLAIN, 1.0, x.data(), 0.0, nullptr, nullptr, nullptr, nullptr, y.data(), -1); break;
+         case 1: spmm(m, K, MM_JACOBI, 1.0, x.data(), 0.0, nullptr, b.data(), dinv.data(), nullptr, y.data(), -1); break;
+         case 2: spmm(m, K, MM_RESID, 1.0, x.data(), 0.0, nullptr, b.data(), nullptr, nullptr, y.data(), -1); break;
+         case 3: amg->pc.amg->apply_multi(b.data(), y.data(), K); break;
+         default: throw Error("unknown kernel kind");
+      }
+   };
+   for (int w = 0; w < 3; w++) launch();
+   hipEvent_t e0, e1;
+   HDA_HIP(hipEventCreate(&e0));
+   HDA_HIP(hipEventCreate(&e1));
+   HDA_HIP(hipEventRecord(e0, ctx.stream));
+   for (int r = 0; r < reps; r++) launch();
+   HDA_HIP(hipEventRecord(e1, ctx.stream));
+   HDA_HIP(hipEventSynchronize(e1));
+   float ms = 0.f;
+   HDA_HIP(hipEventElapsedTime(&ms, e0, e1));
+   (void)hipEventDestroy(e0);
+   (void)hipEventDestroy(e1);
+   if (avg_ms) *avg_ms = (double)ms / std::max(reps, 1);
+   if (bytes) *bytes = kind == 3 ? amg->pc.amg->vcycle_multi_bytes(K) : spmm_bytes(m, K, kind == 0 ? MM_PLAIN : kind == 1 ? MM_JACOBI : MM_RESID, false);
+   HDA_CATCH
 }
 
 // ---------------------------------------------------------------- measurement

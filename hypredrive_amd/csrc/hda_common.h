@@ -266,8 +266,15 @@ struct DCsr {
    mutable DArray<double>         vc_esc;        // vc_escapes (+ padding)
    mutable int                    vc_pack = -1, vc_dict = 0, vc_maxesc = 0; // -1 not examined, 0 code 255 = read val[k], 1 packed; D; most escapes in a chunk
    mutable long long              vc_escapes = 0; // entries outside the first vc_dict dictionary entries
+   // batched products (hda_multi.hip): the rows grouped by lane class -- 4, 8, 16, 32, 64 lanes for rows of at most 8, 16, 32, 64, more
+   // entries -- ascending inside a class; class c owns mrows[mrow_off[c] .. mrow_off[c + 1]).  Built by the first batched product on
+   // the plain arrays alone; mrows_gen: the gen it was built for
+   mutable DArray<int>            mrows;
+   mutable int                    mrow_off[6] = {0, 0, 0, 0, 0, 0};
+   mutable unsigned long long     mrows_gen = 0;
    void reset_plan() const
    {
+      mrows.release(); mrows_gen = 0;
       chunk_row.release(); code.release(); dict_val.release(); dict_delta.release(); offd.reset();
       rclass.release(); rc_keys.release(); lidx.release(); ucol.release(); wmeta.release(); vc_esc.release();
       gen = next_csr_gen();

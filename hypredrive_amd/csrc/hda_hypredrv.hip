@@ -11,6 +11,7 @@
 #include "../../include/HYPREDRV.h"
 
 #include "hda_hypre.h"
+#include "hda_multi.h"
 #include "hda_yaml.h"
 #include "hda_mpi_join.h"
 
@@ -2510,6 +2511,84 @@ extern "C" uint32_t HYPREDRV_LinearSolverApply(HYPREDRV_t h)
    }
    consume_hypre_errors(); // non-convergence is not an error
    API_CATCH_SYNC
+}
+
+// k <= 8 right-hand sides at once (hda_multi.h) against what LinearSolverSetup prepared.  The refusals come first
+// and in an order that needs no device: arguments, then the configuration by key, then the missing Setup.
+extern "C" uint32_t HYPREDRV_AMD_LinearSolverApplyMulti(HYPREDRV_t h, int k, HYPRE_MemoryLocation location, const double *b, double *x,
+                                                        HYPRE_BigInt ld, int *iters, double *final_rel)
+{
+   CHECK_INIT_OBJ(h);
+   err_reset();
+   API_TRY
+   set_stage("HYPREDRV_AMD_LinearSolverApplyMulti");
+   const char *const what = "LinearSolverApplyMulti: ";
+   if (k < 1 || k > kMultiMax) return err_set(ERR_INVALID_VAL, std::string(what) + "k = " + std::to_string(k) + ": 1 to 8 right-hand sides are solved at once");
+   if (!b) return err_set(ERR_INVALID_VAL, std::string(what) + "b is NULL");
+   if (!x) return err_set(ERR_INVALID_VAL, std::string(what) + "x is NULL");
+   if (location != HYPRE_MEMORY_HOST && location != HYPRE_MEMORY_DEVICE)
+      return err_set(ERR_INVALID_VAL, std::string(what) + "location must be HYPRE_MEMORY_HOST or HYPRE_MEMORY_DEVICE");
+   const long long n = h->mat_A ? (long long)h->mat_A->nloc : 0;
+   if (ld < 1 || (long long)ld < n)
+      return err_set(ERR_INVALID_VAL, std::string(what) + "ld = " + std::to_string((long long)ld) + " is smaller than the " + std::to_string(n) +
+                                         " local rows (vector j starts at + j * ld, ld >= n)");
+   static const char *const solver_name[] = {"pcg", "gmres", "fgmres", "bicgstab"};
+   const int sm = h->args.solver.method;
+   if (sm != 0)
+      return err_set(ERR_INVALID_SOLVER, std::string(what) + "solver: " + (sm >= 1 && sm <= 3 ? solver_name[sm] : "this method") +
+                                            " has no batched form; solver: pcg is built");
+   if (h->args.precon().method != 0)
+      return err_set(ERR_INVALID_PRECON, std::string(what) + "preconditioner: " + h->args.precon().method_name +
+                                            " has no batched form; preconditioner: amg is built");
+   if (h->args.solver.scaling.enabled) return err_set(ERR_INVALID_VAL, std::string(what) + "solver.scaling is enabled: the batched solve works on the system as it was given");
+   if (h->num_ns > 0) return err_set(ERR_INVALID_VAL, std::string(what) + "a null-space projection is set (LinearSystemSetNullSpace): not built for the batched solve");
+   if (h->nprocs > 1 || Comm::world().size > 1) return err_set(ERR_INVALID_VAL, std::string(what) + "more than one rank: the batched solve is built on one rank");
+   if (!h->solver || !h->precon || !h->precon_is_setup || !h->mat_A || !h->mat_A->assembled)
+      return err_set(ERR_INVALID_SOLVER, std::string(what) + "no prior HYPREDRV_LinearSolverSetup (solver, preconditioner and matrix must be set up)");
+   if (h->solver->kind != HDA_SOLVER_PCG) return err_set(ERR_INVALID_SOLVER, std::string(what) + "solver: the handle that was set up is not pcg");
+   if (h->precon->kind != HDA_SOLVER_AMG || !h->precon->pc.amg)
+      return err_set(ERR_INVALID_PRECON, std::string(what) + "preconditioner: the handle that was set up is not a BoomerAMG hierarchy");
+   Amg        *amg = h->precon->pc.amg;
+   const DCsr &A   = h->mat_A->A;
+   if (A.ncols != A.nrows) return err_set(ERR_INVALID_VAL, std::string(what) + "the matrix has ghost columns: the batched solve is built on one rank");
+   if (!amg->bound_to(A)) amg->rebind(A, nullptr); // a reused hierarchy takes level 0 from the matrix of the call, as in LinearSolverApply
+   {
+      const std::string why = amg->multi_cycle_refusal();
+      if (!why.empty()) return err_set(ERR_INVALID_PRECON, std::string(what) + "preconditioner: amg: " + why);
+   }
+   const int      nr = A.nrows, K = multi_width(k);
+   DArray<double> B((size_t)std::max(nr, 1) * K), X((size_t)std::max(nr, 1) * K), stage_b, stage_x;
+   const double  *bsrc = b;
+   double        *xsrc = x;
+   long long      lds  = (long long)ld;
+   if (location == HYPRE_MEMORY_HOST)
+   { // the k vectors alone travel, side by side
+      stage_b.alloc((size_t)std::max(nr, 1) * k);
+      stage_x.alloc((size_t)std::max(nr, 1) * k);
+      for (int j = 0; j < k && nr > 0; j++)
+      {
+         HDA_HIP(hipMemcpyAsync(stage_b.data() + (size_t)j * nr, b + (size_t)j * (size_t)ld, sizeof(double) * (size_t)nr, hipMemcpyHostToDevice, Context::get().stream));
+         HDA_HIP(hipMemcpyAsync(stage_x.data() + (size_t)j * nr, x + (size_t)j * (size_t)ld, sizeof(double) * (size_t)nr, hipMemcpyHostToDevice, Context::get().stream));
+      }
+      Context::get().sync();
+      bsrc = stage_b.data();
+      xsrc = stage_x.data();
+      lds  = nr;
+   }
+   multi_pack(nr, k, K, bsrc, lds, B.data());
+   multi_pack(nr, k, K, xsrc, lds, X.data());
+   const std::vector<KrylovResult> res = pcg_multi(A, amg, h->solver->kp, k, B.data(), X.data());
+   multi_unpack(nr, k, K, X.data(), xsrc, lds);
+   if (location == HYPRE_MEMORY_HOST)
+      for (int j = 0; j < k && nr > 0; j++)
+         HDA_HIP(hipMemcpyAsync(x + (size_t)j * (size_t)ld, stage_x.data() + (size_t)j * nr, sizeof(double) * (size_t)nr, hipMemcpyDeviceToHost, Context::get().stream));
+   Context::get().sync();
+   for (int j = 0; j < k; j++)
+   {
+      if (iters) iters[j] = res[(size_t)j].iters;
+      if (final_rel) final_rel[j] = res[(size_t)j].final_rel;
+   }
+   API_CATCH
 }
 
 extern "C" uint32_t HYPREDRV_PreconApply(HYPREDRV_t h, HYPRE_Vector b, HYPRE_Vector x)

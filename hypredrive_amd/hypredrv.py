@@ -82,6 +82,7 @@ def lib():
         "HYPREDRV_AMD_SolvePhaseBytes": [vp, dp, dp],
         "HYPREDRV_AMD_LastResidualNorms": [vp, dp, dp, ip],
         "HYPREDRV_AMD_ProbeDominant": [vp, C.c_int, ip, dp, dp, ip],
+        "HYPREDRV_AMD_LinearSolverApplyMulti": [vp, C.c_int, C.c_int, vp, vp, C.c_longlong, ip, dp],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -354,6 +355,38 @@ class Hypredrv:
             check(lib().HYPREDRV_LinearSystemResetInitialGuess(self.h))
         check(lib().HYPREDRV_LinearSolverApply(self.h))
         return self.last()
+
+    def apply_multi(self, k, b, x, ld, location=MEMORY_HOST, iters=None, final_rel=None):
+        """HYPREDRV_AMD_LinearSolverApplyMulti as it is declared: b, x raw addresses (ints or None), iters / final_rel ctypes pointers"""
+        check(lib().HYPREDRV_AMD_LinearSolverApplyMulti(self.h, k, location, b, x, ld, iters, final_rel))
+
+    def solve_multi(self, B, X0=None, device=False, ld=None, k=None):
+        """k <= 8 right-hand sides (the columns of B, n x k) through one pass over every operator, against what create_and_setup
+        prepared.  X0: the initial guesses (zero by default); ld: the distance between two vectors in the arrays handed to the
+        library (n by default).  device=True: B and X0 are device arrays (DeviceBuffer, torch-ROCm tensor) that hold k vectors one
+        after the other, vector j at element j * ld (k: how many of them, all that B holds by default); X0 is overwritten with
+        the solutions and returned as it is.  Returns (X, iters, final_rel)."""
+        if device:
+            from ._lib import device_pointer
+            if X0 is None or ld is None:
+                raise ValueError("solve_multi(device=True) needs X0 (in / out) and ld")
+            k = _count(B) // int(ld) if k is None else int(k)
+            it, fr = np.zeros(max(k, 1), dtype=np.int32), np.zeros(max(k, 1))
+            self.apply_multi(k, device_pointer(B), device_pointer(X0), int(ld), MEMORY_DEVICE, it.ctypes.data_as(C.POINTER(C.c_int)),
+                             fr.ctypes.data_as(C.POINTER(C.c_double)))
+            return X0, it[:k].copy(), fr[:k].copy()
+        B = np.asarray(B, dtype=np.float64)
+        B = B.reshape(-1, 1) if B.ndim == 1 else B
+        n, k = B.shape
+        ld = n if ld is None else int(ld)
+        bt, xt = np.zeros((max(k, 1), ld)), np.zeros((max(k, 1), ld))
+        bt[:k, :n] = B.T
+        if X0 is not None:
+            xt[:k, :n] = np.asarray(X0, dtype=np.float64).reshape(n, k).T
+        it, fr = np.zeros(max(k, 1), dtype=np.int32), np.zeros(max(k, 1))
+        self.apply_multi(k, bt.ctypes.data, xt.ctypes.data, ld, MEMORY_HOST, it.ctypes.data_as(C.POINTER(C.c_int)),
+                         fr.ctypes.data_as(C.POINTER(C.c_double)))
+        return xt[:k, :n].T.copy(), it[:k].copy(), fr[:k].copy()
 
     def destroy_solver(self):
         check(lib().HYPREDRV_LinearSolverDestroy(self.h))

@@ -176,6 +176,18 @@ HYPREDRV_EXPORT_SYMBOL uint32_t HYPREDRV_AMD_ProbeDominant(HYPREDRV_t hypredrv, 
 /* Read-only HBM view of the owned entries of an IJ vector (*n of them), valid until the vector is next modified or destroyed: the
  * solution of HYPREDRV_LinearSystemGetSolution without the host mirror.  Does not count as a modification of the vector. */
 HYPREDRV_EXPORT_SYMBOL uint32_t HYPREDRV_AMD_IJVectorDevicePointer(HYPRE_IJVector vec, const double **ptr, HYPRE_Int *n);
+/* k <= 8 right-hand sides through one pass over every operator, against the operator and the preconditioner that
+ * HYPREDRV_LinearSolverSetup prepared; the reuse policy does not see the call, no row is added to the statistics table and the
+ * system's own rhs / solution vectors and init_guess_mode are not touched.  b, x: host pointers (HYPRE_MEMORY_HOST) or device
+ * pointers (HYPRE_MEMORY_DEVICE); vector j starts at + j * ld, ld >= the local rows.  x holds the initial guesses on entry and the
+ * solutions on exit.  iters, final_rel: k entries each, or NULL.  Column by column the result is that of HYPREDRV_LinearSolverApply
+ * (same stopping test, same iteration count).  Built: solver pcg with preconditioner amg -- Jacobi-family smoothers, relaxation
+ * points all, one row block -- on one rank.  Refused with the sticky error state and a message that names the key: solver gmres /
+ * fgmres / bicgstab, every other preconditioner, solver.scaling enabled, a null-space projection, more than one rank, no prior
+ * Setup, null pointers, ld < n, k outside 1 .. 8. */
+HYPREDRV_EXPORT_SYMBOL uint32_t HYPREDRV_AMD_LinearSolverApplyMulti(HYPREDRV_t hypredrv, int k, HYPRE_MemoryLocation location,
+                                                                    const double *b, double *x, HYPRE_BigInt ld, int *iters,
+                                                                    double *final_rel);
 
 #ifdef __cplusplus
 }

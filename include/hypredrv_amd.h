@@ -325,6 +325,38 @@ int hda_fgmres(hda_csr_t A, hda_amg_t amg, const hda_krylov_params *kp, const do
 int hda_bicgstab(hda_csr_t A, hda_amg_t amg, const hda_krylov_params *kp, const double *b, double *x,
               double *hist, int *iters, int *converged, double *final_rel);
 
+/* ---- up to 8 right-hand sides at once ---------------------------- */
+/* Host arrays of these entries are column-major: k vectors of n doubles each, vector j at base + j * n.  On the device the k vectors
+ * are interleaved over K = 2, 4 or 8 columns (the smallest that holds k); the padding columns are zero and never come back.
+ * 1 <= k <= 8, one rank; anything else is refused by name. */
+/* One batched product on the plain CSR arrays of A.  mode:
+ *   HDA_SPMM_PLAIN   Y = alpha A X + beta Yin   (Yin NULL with beta == 0)
+ *   HDA_SPMM_RESID   Y = B - A X
+ *   HDA_SPMM_JACOBI  Y = X + dinv .* (B - A X), dinv one divisor per row for all columns (ncols >= nrows)
+ * W != NULL: dots[j] = <W_j, Y_j> (dots: k doubles).  X: k x ncols; Yin, B, W, Y: k x nrows; dinv: nrows.  Y is in / out: rows the
+ * product does not write come back as they were given. */
+enum { HDA_SPMM_PLAIN = 0, HDA_SPMM_RESID = 1, HDA_SPMM_JACOBI = 2 };
+int hda_spmm(hda_csr_t A, int mode, int k, double alpha, double beta, const double *X, const double *Yin, const double *B, const double *dinv,
+             const double *W, double *Y, double *dots);
+/* The batched BLAS-1 of the PCG recurrences on k vectors of n.  alpha, beta, active: k entries; a column whose active flag is 0 gets
+ * alpha_j = beta_j = 0 from the scalar kernel.  op:
+ *   HDA_MBLAS_DOT     out[j] = <U_j, V_j>                                           (U, V in; out: k doubles)
+ *   HDA_MBLAS_UPDATE  U += alpha_j P, V -= alpha_j S; out[j] = <V_j, V_j> afterwards  (U = x, V = r in / out; P, S in)
+ *   HDA_MBLAS_DIR     U = P + beta_j U                                              (U = p in / out, P = z in) */
+enum { HDA_MBLAS_DOT = 0, HDA_MBLAS_UPDATE = 1, HDA_MBLAS_DIR = 2 };
+int hda_multi_blas(int op, int k, int n, const double *alpha, const double *beta, const int *active, const double *P, const double *S, double *U,
+                   double *V, double *out);
+/* One V-cycle from a zero guess on k right-hand sides (Amg::apply_multi): Jacobi-family smoothers (0, 7, 18), relaxation points all,
+ * coarsest level by ge or Jacobi sweeps, one row block; anything else is refused by name here, never at setup.  B, X: k x n. */
+int hda_amg_vcycle_multi(hda_amg_t amg, int k, const double *B, double *X);
+/* k PCG recurrences in lockstep, each of them hda_pcg on its column (amg: a hierarchy within the limits above, or NULL).  B, X: k x n,
+ * X in / out; hist: k x (max_iter + 1) doubles (may be NULL); iters, converged, final_rel: k entries (may be NULL). */
+int hda_pcg_multi(hda_csr_t A, hda_amg_t amg, const hda_krylov_params *kp, int k, const double *B, double *X, double *hist, int *iters,
+                  int *converged, double *final_rel);
+/* hda_time_kernel for the batched kernels, vectors resident in HBM: kind 0 the batched product of A, 1 its Jacobi sweep, 2 its
+ * residual, 3 one batched V-cycle (needs amg).  Average milliseconds per launch and algorithmic bytes per launch. */
+int hda_time_kernel_multi(int kind, hda_csr_t A, hda_amg_t amg, int k, int reps, double *avg_ms, double *bytes);
+
 /* ---- measurement (bench.py) -------------------------------------------------------- */
 /* Times `reps` launches of one kernel with HIP events on the library's stream, vectors
  * resident in HBM.  kind: 0 SpMV, 1 l1-Jacobi sweep, 2 residual, 3 V-cycle (needs amg).

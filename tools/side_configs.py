@@ -22,7 +22,12 @@ iteration count == oracle's.  bench.py carries them as budgeted extras; `python 
                   beside the l1-Jacobi sweep on the same A (`python tools/side_configs.py fsai 128`)
   assemble N      not a BASELINE config: the N^3 7-point Laplacian assembled four ways -- host IJ calls, SetMatrixFromCSR, device pointers
                   in CSR order, device pointers as shuffled finite-element-style adds: ms of each, and the sort and
-                  run-reduce kernels of the last on their own (`python tools/side_configs.py assemble 128`)"""
+                  run-reduce kernels of the last on their own (`python tools/side_configs.py assemble 128`)
+  multirhs N      not a BASELINE config: k = 2, 4, 8 right-hand sides at once on the N^3 7-point Laplacian -- the
+                  batched Jacobi sweep on the level-1 operator beside the single sweep (bytes / time), and ms per right-hand side
+                  through HYPREDRV_AMD_LinearSolverApplyMulti beside k consecutive HYPREDRV_LinearSolverApply calls; two child
+                  processes, one with HDA_CODED=0 HDA_WINDOW=0 on the single path (what a general matrix gets), one with the defaults
+                  (`python tools/side_configs.py multirhs 128`)"""
 import json
 import os
 import sys
@@ -383,10 +388,100 @@ def assemble(hh, n=128, reps=5, warmup=1, ways="abcd"):
     return out
 
 
+YAML_MULTI = "solver:\n  pcg:\n    relative_tol: 1.0e-8\npreconditioner: amg\n"
+
+
+def multi_rhs_arm(hh, n=128, rounds=5, reps=20):
+    """One process of `multirhs`: the single path runs under this process's HDA_CODED / HDA_WINDOW, the batched path reads neither.
+    Rounds interleave the variants; medians and minima over the rounds."""
+    from hypredrive_amd import hypredrv as hd
+    from hypredrive_amd._lib import DeviceBuffer, borrow
+    N = n ** 3
+    h = hd.Hypredrv(YAML_MULTI)
+    h.set_laplacian7((n, n, n))
+    h.finish_system()
+    h.create_and_setup()
+    A, amg = borrow(h)
+    med = lambda v: float(np.median(v))
+    out = {"rows": N, "levels": amg.num_levels, "env": {k: os.environ.get(k) for k in ("HDA_CODED", "HDA_WINDOW")}}
+    # ---- the dominant kernel: the Jacobi sweep on level 1, single beside K = 2, 4, 8
+    A1 = amg.level_matrix(1, 0)
+    sweeps = {"single": []}
+    sweeps.update({f"K{K}": [] for K in (2, 4, 8)})
+    nbytes = {}
+    for _ in range(rounds):
+        ms, nbytes["single"] = hh.time_kernel(1, A1, reps=reps)
+        sweeps["single"].append(ms)
+        for K in (2, 4, 8):
+            ms, nbytes[f"K{K}"] = hh.time_kernel_multi(1, A1, K, reps=reps)
+            sweeps[f"K{K}"].append(ms)
+    out["level1"] = {"rows": A1.nrows, "nnz": A1.nnz, "single_form": hh._lib.csr_form(A1)["kernel"], "sweep": {
+        name: {"ms": med(v), "ms_min": float(min(v)), "bytes": nbytes[name], "gbs": nbytes[name] / med(v) / 1e6,
+               "ms_per_rhs": med(v) / (1 if name == "single" else int(name[1:]))} for name, v in sweeps.items()}}
+    # ---- solves: k consecutive applies beside one batched apply on the same right-hand sides
+    rng = np.random.default_rng(1)
+    t = np.arange(N) / N
+    B = np.empty((8, N))
+    B[0] = np.sin(2.0 * np.pi * t)
+    B[1] = 1.0
+    for j in range(2, 8):
+        B[j] = rng.standard_normal(N)
+    Bd = DeviceBuffer.from_numpy(B.ravel())
+    singles = {k: [] for k in (2, 4, 8)}
+    batch = {k: [] for k in (2, 4, 8)}
+    iters = {}
+    for rnd in range(rounds + 1):  # (round 0 warms both paths up and is dropped)
+        one = []
+        it1 = []
+        for j in range(8):
+            h.set_rhs_array(0, N - 1, B[j])
+            r = h.apply()
+            one.append(r["solve_s"] * 1e3)
+            it1.append(r["iters"])
+        for k in (2, 4, 8):
+            Xd = DeviceBuffer.from_numpy(np.zeros(k * N))
+            hh.sync()
+            t0 = time.perf_counter()
+            _, itk, _ = h.solve_multi(Bd, X0=Xd, device=True, ld=N, k=k)
+            hh.sync()
+            ms = (time.perf_counter() - t0) * 1e3
+            if rnd:
+                singles[k].append(sum(one[:k]))
+                batch[k].append(ms)
+            iters[k] = {"single": it1[:k], "batch": [int(v) for v in itk]}
+    out["solve"] = {str(k): {"single_ms_per_rhs": med(singles[k]) / k, "batch_ms_per_rhs": med(batch[k]) / k, "single_ms": med(singles[k]),
+                             "batch_ms": med(batch[k]), "batch_ms_min": float(min(batch[k])), "single_ms_min": float(min(singles[k])),
+                             "speedup": med(singles[k]) / med(batch[k]), "iters": iters[k]} for k in (2, 4, 8)}
+    h.destroy_solver()
+    h.close()
+    return out
+
+
+def multi_rhs(n=128):
+    """Both arms of `multirhs`, each in a fresh child process (HDA_CODED is read once per process)."""
+    import subprocess
+    arms = {}
+    for name, env in (("a_general_matrix", {"HDA_CODED": "0", "HDA_WINDOW": "0"}), ("b_defaults", {})):
+        e = {k: v for k, v in os.environ.items() if k not in ("HDA_CODED", "HDA_WINDOW")}
+        e.update(env)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "multirhs-arm", str(n)], env=e, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"multirhs arm {name} failed:\n{r.stderr[-2000:]}")
+        arms[name] = json.loads(r.stdout.strip().splitlines()[-1])
+    k4 = arms["a_general_matrix"]["solve"]["4"]
+    return {"what": f"k right-hand sides at once on the {n}^3 7-point Laplacian, PCG(1e-8) + BoomerAMG defaults", "arms": arms,
+            "required_a_k4_batch_faster": bool(k4["batch_ms"] < k4["single_ms"])}
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "multirhs":
+        print(json.dumps(multi_rhs(int(sys.argv[2]) if len(sys.argv) > 2 else 128)))
+        sys.exit(0)
     import hypredrive_amd as hh
     which = sys.argv[1] if len(sys.argv) > 1 else "mgr"
-    if which == "assemble":
+    if which == "multirhs-arm":
+        print(json.dumps(multi_rhs_arm(hh, int(sys.argv[2]) if len(sys.argv) > 2 else 128)))
+    elif which == "assemble":
         print(json.dumps(assemble(hh, int(sys.argv[2]) if len(sys.argv) > 2 else 128, ways=sys.argv[3] if len(sys.argv) > 3 else "abcd")))
     elif which == "schwarz":
         print(json.dumps(gmres_schwarz(hh, int(sys.argv[2]) if len(sys.argv) > 2 else 128)))
